@@ -1,6 +1,7 @@
 """Benchmark: aggregate Gibbs sweeps/s (+ ESS/s) on J1713+0747, batched chains per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--chains C] [--config 2|3|4|5]
+                    [--dump-outputs DIR] [--full]
 
 A *step* is one Gibbs sweep (gibbs.py:354-380) of every chain on every rank.  Each rank owns
 C chains (weak scaling; default 2048 per GPU = two chains per SIMD, the "1024+ batched
@@ -16,8 +17,23 @@ anything touches a GPU and relays rank 0's JSON line.  Chains never communicate 
 sampling; the collectives are the final all-gather of every chain's post-burn-in draws
 (global split-R-hat and bulk-ESS over ALL chains) and a max-reduce of the timings.
 
-Order of a run: W warmup sweeps, the timed region (K sweeps), then ``--ess-burn`` burn-in
-sweeps (untimed, discarded) and the ESS window.  The burn-in runs AFTER the timed region:
+A plain run does only what the headline figure needs: it sets up, runs W warmup sweeps and
+the timed region (K sweeps), writes the timed region's last step with ``--dump-outputs DIR``
+and prints the result line.  ``--dump-outputs DIR`` writes, as float64 ``DIR/<name>.npy``,
+what a caller of the timed launch receives for its last sweep: the chain state after it
+(``x b z alpha pout theta nu status``) and the last row of every record array
+(``rec_<key>``), with ``chain_index`` naming the chains written (all of them, or a fixed
+seeded sample when they would exceed 64 MB); with several ranks each rank writes
+``<name>_rank<r>.npy``.  Inputs, seeds and Philox keys are fixed by the arguments, so two
+builds can be compared array for array.
+
+Everything else is measured only with ``--full``: the CPU baseline, the ESS window with
+its global R-hat / ESS, and the stage-masked launches behind the per-stage roofline
+figures; without it those fields of the result line are null.
+
+Order of a ``--full`` run: the CPU baseline, W warmup sweeps, the timed region (K sweeps),
+then ``--ess-burn`` burn-in sweeps (untimed, discarded), the ESS window and the stage-masked
+launches.  The burn-in runs AFTER the timed region:
 MI355X lowers its shader clock after ~1 s of full load (2.37 -> 2.06 GHz, recovering over
 ~20 ms of further work; tools/diag/after_burn.py), so a short timed launch right after a
 long burn-in launch measures the power manager, not the kernel.  ESS/s has its own window,
@@ -525,6 +541,33 @@ def ess_rate(ess, rhat, seconds):
     return None, "n/a"
 
 
+DUMP_BUDGET_BYTES = 60e6     # --dump-outputs: under 64 MB in all
+DUMP_SAMPLE_SEED = 64
+
+
+def dump_outputs(dirname: str, state: dict, rec: dict, rank: int, world: int):
+    """Write the timed region's last step (module docstring) as float64 .npy files."""
+    os.makedirs(dirname, exist_ok=True)
+    C = int(next(iter(state.values())).shape[0])
+    per_chain = 8 * (1 + sum(int(np.prod(v.shape[1:])) for v in state.values())
+                     + sum(int(np.prod(v.shape[2:])) for v in rec.values()))
+    keep = int(DUMP_BUDGET_BYTES // per_chain)
+    idx = np.arange(C)
+    if keep < C:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(C, keep, replace=False))
+    sfx = "" if world == 1 else f"_rank{rank}"
+    arrays = dict(state)
+    arrays.update({"rec_" + k: v[:, -1] for k, v in rec.items()})
+    np.save(os.path.join(dirname, f"chain_index{sfx}.npy"), idx.astype(np.float64))
+    for k, v in arrays.items():
+        if hasattr(v, "detach"):      # a tensor: pick the chains on its device, then copy
+            import torch
+            v = v.detach()[torch.as_tensor(idx, device=v.device)].cpu().numpy()
+        else:
+            v = np.asarray(v)[idx]
+        np.save(os.path.join(dirname, f"{k}{sfx}.npy"), np.asarray(v, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -535,11 +578,18 @@ def main():
     ap.add_argument("--chains", type=int, default=None,
                     help="chains per GPU (config 4: per dataset)")
     ap.add_argument("--seed", type=int, default=20171713)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed region's last step (chain state after it and the "
+                         "last record row) as float64 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU baseline, the ESS window (global R-hat / "
+                         "ESS) and the stage-masked launches; a plain run only times the "
+                         "steps")
     ap.add_argument("--ess-burn", type=int, default=None,
-                    help="extra discarded sweeps before the ESS window (default 3000; "
+                    help="--full: extra discarded sweeps before the ESS window (default 3000; "
                          "config 5: no ESS window)")
     ap.add_argument("--ess-window", type=int, default=None,
-                    help="sweeps of the ESS window (default 5000; config 5: 0)")
+                    help="--full: sweeps of the ESS window (default 5000; config 5: 0)")
     ap.add_argument("--ess-thin", type=int, default=5,
                     help="record every k-th sweep of the ESS window (default 5)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -561,14 +611,15 @@ def main():
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus, sys.argv[1:])     # before anything touches a GPU
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.stub:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.stub:
         cores = max(1, min(16 if args.config != 5 else 8, os.cpu_count() or 1))
         secs = args.cpu_seconds if args.config != 5 else max(args.cpu_seconds, 20.0)
         cpu = cpu_baseline(args.config, secs, cores)      # before the GPU is touched
     ess_burn = args.ess_burn if args.ess_burn is not None else (0 if args.config == 5 else 3000)
     ess_win = args.ess_window if args.ess_window is not None else (0 if args.config == 5 else 5000)
     thin = max(1, args.ess_thin)
-    ess_win = (ess_win // thin) * thin
+    ess_win = (ess_win // thin) * thin if args.full else 0
+    stage_costs_on = args.full and not args.no_stage_costs
 
     import torch
     rank, local, world = dist.init("gloo" if args.stub else None)
@@ -625,6 +676,9 @@ def main():
     # low-rank path updates (z at the start of each sweep is the z its Gram uses)
     gram_paths = None if args.stub else ns.gram_counts(reset=True)
     zflag = float(rec["z"].sum(dim=-1).mean()) if "z" in rec else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     {"x": ns.x, "theta": ns.theta} if args.stub else ns.state, rec, rank, world)
     del rec
     if large:
         ns.set_timing(False)
@@ -646,7 +700,7 @@ def main():
                                        sweep0=W + K + burn, chain0=c0))
         nflw = (np.asarray(ns.get_state()["status"]) >> 8) - nfl0
         floor_win = np.array([float((nflw > 0).sum()), float(nflw.sum())])
-        if not large and not args.stub and not args.no_stage_costs:   # at the working clock
+        if not large and not args.stub and stage_costs_on:   # at the working clock
             stage_ms = stage_costs(ns, max(1, min(K, 200)), args.seed, W + K + burn + ess_win,
                                    c0)
         draws = dist.gather_chains(torch.cat([wrec["x"], wrec["theta"][..., None]], dim=2)
@@ -663,7 +717,7 @@ def main():
             by_group = res[2] if groups is not None else None
             conv_group = res[3] if groups is not None else None
         del wrec, draws
-    if stage_ms is None and not large and not args.stub and not args.no_stage_costs:
+    if stage_ms is None and not large and not args.stub and stage_costs_on:
         stage_ms = stage_costs(ns, max(1, min(K, 200)), args.seed, W + K + burn + ess_win, c0)
     shards = dist.gather_chains(np.array([[c0, c0 + C]], dtype=np.float64), dev)
     m_vec = np.array([elapsed, kernel_ms, win_s])
@@ -793,7 +847,8 @@ def main():
                         v[k2.replace("tflops", "frac")] = v[k2] / FP64_PEAK_TFLOPS
         ess_ps, reason = None, None
         if ess is None:
-            reason = "no ESS window (config 5: 155 ms per sweep)" if ess_win <= 0 else "n/a"
+            reason = ("not measured: the ESS window runs with --full" if not args.full else
+                      "no ESS window (config 5: 155 ms per sweep)" if ess_win <= 0 else "n/a")
         else:
             # ESS over every chain of the job / the window's wall time (max over ranks)
             ess_ps, reason = ess_rate(ess, rhat, win_s)

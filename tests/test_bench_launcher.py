@@ -12,18 +12,70 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*args):
+def _run(*args, full=True):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub",
                           "--steps", "6", "--warmup", "2", "--ess-burn", "4",
-                          "--ess-window", "60", *args], env=env, capture_output=True,
-                         text=True, timeout=600)
+                          "--ess-window", "60", *(["--full"] if full else []), *args],
+                         env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout
     return json.loads(lines[0])
+
+
+def test_plain_run_times_the_steps_only_and_dumps_its_last_step(tmp_path):
+    """Without --full no ESS window is run (its fields are null) and the result line keeps
+    the headline fields; --dump-outputs writes the last timed step as float64 arrays that
+    two runs with the same arguments reproduce exactly."""
+    import numpy as np
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    one = _run("--chains", "5", "--dump-outputs", a, full=False)
+    _run("--chains", "5", "--dump-outputs", b, full=False)
+    assert one["steps"] == 6 and one["warmup"] == 2
+    assert one["unit"] == "chain-sweeps/s" and one["higher_is_better"] is True
+    assert one["dtype"] == "f64" and one["value"] > 0 and one["ms_per_step"] > 0
+    assert one["ess_per_sec"] is None and one["cpu_baseline"] is None
+    assert one["ess_window"]["sweeps"] == 0 and one["ess_window"]["ess_total"] is None
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b))
+    assert {"chain_index.npy", "rec_x.npy", "rec_theta.npy", "theta.npy", "x.npy"} <= set(names)
+    assert np.array_equal(np.load(os.path.join(a, "chain_index.npy")), np.arange(5.0))
+    for nm in names:
+        va, vb = np.load(os.path.join(a, nm)), np.load(os.path.join(b, nm))
+        assert va.dtype == np.float64 and va.shape[0] == 5
+        assert np.array_equal(va, vb), nm
+    # the stub records a sweep's state before it moves the chain: the last record differs
+    # from the state after the last step, and both are finite
+    x, rx = np.load(os.path.join(a, "x.npy")), np.load(os.path.join(a, "rec_x.npy"))
+    assert x.shape == rx.shape and np.isfinite(x).all() and not np.array_equal(x, rx)
+
+
+def test_dump_outputs_samples_chains_beyond_its_budget(tmp_path, monkeypatch):
+    """Past the size budget --dump-outputs keeps a fixed, seeded, sorted sample of the chains,
+    the same rows of every array, and names them in chain_index."""
+    import numpy as np
+
+    import bench
+    C = 40
+    state = {"x": np.arange(C * 3, dtype=np.float64).reshape(C, 3),
+             "status": np.arange(C, dtype=np.int32)}
+    rec = {"x": np.arange(C * 2 * 3, dtype=np.float64).reshape(C, 2, 3)}
+    per_chain = 8 * (1 + 3 + 1 + 3)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * per_chain + 1)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), state, rec, 0, 1)
+    got = {nm[:-4]: np.load(str(tmp_path / "a" / nm)) for nm in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["chain_index", "rec_x", "status", "x"]
+    idx = got["chain_index"].astype(int)
+    assert len(idx) == 10 and np.all(np.diff(idx) > 0) and idx.max() < C
+    assert np.array_equal(got["x"], state["x"][idx])
+    assert np.array_equal(got["rec_x"], rec["x"][idx, -1])
+    assert got["status"].dtype == np.float64 and np.array_equal(got["status"], idx)
+    assert sum(v.nbytes for v in got.values()) <= 10 * per_chain + 1
+    assert np.array_equal(np.load(str(tmp_path / "b" / "chain_index.npy")), got["chain_index"])
 
 
 def test_two_rank_launch_matches_one_process():

@@ -24,7 +24,8 @@ def _bench(*args):
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"),
                           "--steps", "8", "--warmup", "2", "--ess-burn", "20",
-                          "--ess-window", "100", "--no-cpu-baseline", "--no-stage-costs", *args],
+                          "--ess-window", "100", "--full", "--no-cpu-baseline",
+                          "--no-stage-costs", *args],
                          env=env, capture_output=True, text=True, timeout=100)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

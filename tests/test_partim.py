@@ -1,8 +1,8 @@
 """The runtime tempo2 par/tim reader (gibbs_student_t_amd/partim.py).
 
-* Against the reference's own J1713+0747 files (read in the build container only; the
-  test skips where /root/reference is absent): the reader reproduces the packed
-  data/J1713+0747.npz the sampler's J1713 dataset is built from, array for array.
+* Against the reference's own J1713+0747 data files (copies under tests/golden/): the
+  reader reproduces the packed data/J1713+0747.npz the sampler's J1713 dataset is built
+  from, array for array.
 * A synthetic pulsar written by the test (comments, commands, flags, INCLUDE, sexagesimal
   coordinates) round-trips.
 Parity with tempo2 itself (clock corrections, barycentring, the design matrix) is
@@ -15,11 +15,9 @@ import pytest
 
 from gibbs_student_t_amd import data, partim
 
-REF = "/root/reference"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "J1713+0747.tim")),
-                    reason="reference data files are only in the build container")
 def test_reader_reproduces_packed_j1713():
     raw = partim.load_raw(os.path.join(REF, "J1713+0747.par"),
                           os.path.join(REF, "J1713+0747.tim"), os.path.join(REF, "red.txt"))
@@ -60,8 +58,6 @@ def test_synthetic_partim_round_trip(tmp_path):
     assert M.shape == (3, 1 + 4)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "J1713+0747.tim")),
-                    reason="reference data files are only in the build container")
 def test_load_partim_equals_packed_dataset():
     """The runtime loader builds the same J1713 dataset as the packed npz (bit for bit)."""
     a = data.j1713(seed=5, red_source="red.txt")

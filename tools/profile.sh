@@ -5,8 +5,8 @@
 # then: python tools/pmc_json.py gpurun_out/prof_$ROUND 200 2048 > profiles/${ROUND}_pmc_config2.json
 source tools/gpu_step.sh
 O=gpurun_out/prof_${ROUND:-r5}; mkdir -p $O
-step 300 $O/bench_driver.json python bench.py --steps 20 --warmup 5
-B="python bench.py --no-cpu-baseline"
+step 300 $O/bench_driver.json python bench.py --full --steps 20 --warmup 5
+B="python bench.py --full --no-cpu-baseline"
 step 300 $O/bench_s500.json $B --steps 500 --warmup 100
 step 300 $O/bench_c1024.json $B --steps 500 --warmup 100 --chains 1024
 step 200 $O/bench_c3.json $B --config 3 --steps 500 --warmup 100
