@@ -31,6 +31,7 @@
 namespace gst {
 
 constexpr int LBLK = 256;      // threads of the per-chain kernels (4 waves)
+constexpr double LN10 = 2.302585092994045684;
 // threads per chain of the per-TOA passes (lg_white, lg_toa): 16 waves per chain for the
 // 100k-TOA datasets; 4 for datasets of up to TBLK_SMALL_NPAD TOAs, where a pass is a few
 // TOAs per thread and a 16-wave chain spent it in barriers and reductions with one chain per
@@ -288,7 +289,7 @@ __device__ __forceinline__ void mh_variate(const DevModel& md, const Rng& rng, c
   out4[0] = par;
   out4[1] = delta;
   out4[2] = la;
-  out4[3] = exp(2.0 * delta * 2.302585092994045684);
+  out4[3] = exp(2.0 * delta * LN10);
 }
 
 typedef double XVec[PMAX];   // a chain's parameter vector (x, or an MH proposal)
@@ -362,7 +363,7 @@ __device__ __forceinline__ WhiteNoise white_noise(const DevModel& md, const XVec
       const double xe = xget(x, ei >= 0 ? ei : 0);
       const double ef = ei >= 0 ? xe : md.efac_const;
       w.ef2[b] = ef * ef;
-      w.Q[b] = exp(2.0 * xget(x, md.equad_b[b]) * 2.302585092994045684);
+      w.Q[b] = exp(2.0 * xget(x, md.equad_b[b]) * LN10);
     } else {
       w.ef2[b] = 0.0;
       w.Q[b] = 0.0;
@@ -546,7 +547,6 @@ __global__ void __launch_bounds__(TB) lg_white(const DevModel* __restrict__ mds,
     // (three proposals' parameter vectors and variance sets held there cost ~190 registers
     // and spilled).  A proposal is (x0, Q0) moved by its step's jump; Q of a one-backend
     // model is carried multiplicatively (Q0 10^(2 delta) when the step moves equad).
-    constexpr double LN10 = 2.302585092994045684;
     auto propose = [&](int step, const XVec& x0, double Q0, XVec& qv, double& Qq)
         __attribute__((always_inline)) {
       const int par = (int)mhv[step][0];
@@ -1225,12 +1225,237 @@ __global__ void __launch_bounds__(LBLK) lg_tmelim(const DevModel* __restrict__ m
 }
 
 // ------------------------------------------------------------------------------------
-// hyper: red-noise MH on S0 + diag(phi^-1) in LDS; b draw's Fourier block
+// hyper: what the one-wave kernels lg_hyper_reg and lg_hyper_ecr share.  They differ in how
+// they eliminate Sigma (each one's lnl callable), in their b draw and in where the floor's
+// pivots come from; the prologue, the prior side of the likelihood, the MH loop and the
+// epilogue are the code below for both.  lg_hyper (256 threads per chain) has the same steps
+// written out in its body: on this code its blocked mode measured 1.7% slower.
 // ------------------------------------------------------------------------------------
-struct HyperLds {
-  double* S;    // [ms][SS] working factor (raw columns), row-major lower
-  int SS;
+struct HyperIn {   // a chain's inputs, filled once
+  double* sc;
+  double fsh;      // floor pass: the chain's SVD noise floor f (Sigma + f I); else 0
+  bool skip;       // floor pass, and this chain's b draw needed no floor
+  Rng rng;
+  const double* tp;
+  double logdetN, rNr, x_last0;
+  double ld_tm, quad_tm;   // lg_tmelim's terms (0 where the kernel factors the timing model)
+  int fail_tm;
 };
+
+// tm: lg_tmelim eliminated the chain's timing model; thread t of the chain fills mhv [NHYPER][4]
+__device__ __forceinline__ HyperIn hyper_in(const DevModel& md, const LArgs& a, int c, bool tm,
+                                            int t, double* mhv) {
+  HyperIn in{};
+  in.sc = a.s.sc + (size_t)c * 16;
+  // floor pass: only the chains whose b draw runs at the SVD noise floor (SC_FLOOR > 0)
+  in.fsh = a.floor_pass ? in.sc[SC_FLOOR] : 0.0;
+  in.skip = a.floor_pass && !(in.fsh > 0.0);
+  if (in.skip) return in;
+  in.rng = make_rng(a, c);
+  in.tp = tape_row(a, c);
+  in.logdetN = in.sc[SC_LOGDETN];
+  in.rNr = in.sc[SC_RNR];
+  in.x_last0 = in.sc[SC_XLAST];
+  in.ld_tm = tm ? in.sc[SC_LDTM] : 0.0;
+  in.quad_tm = tm ? in.sc[SC_QUADTM] : 0.0;
+  in.fail_tm = tm ? in.sc[SC_FAILTM] != 0.0 : 0;
+  if (!a.eval_only && !a.floor_pass && t < NHYPER)
+    mh_variate(md, in.rng, in.tp, NWHITE + t, mhv + 4 * t);
+  return in;
+}
+
+// the prior side of the b-marginalised lnL (gibbs.py:288-329): log of the power law's
+// coefficient, log|phi| (its Fourier and timing-model part, then with the ECORR columns backend
+// by backend), phi^-1 of hyper column jc < nf + nec (+ f in the floor pass), and the sum
+__device__ __forceinline__ double hyper_lc(const DevModel& md, double lA, double g) {
+  return 2.0 * lA * LN10 - md.log_12pi2 + (g - 3.0) * md.log_fyr;
+}
+__device__ __forceinline__ double hyper_logdet_phi0(const DevModel& md, double lc, double g) {
+  return ((double)md.nf * lc - g * md.sum_lfreq + md.sum_ldf) + md.logdet_phi_tm;
+}
+__device__ __forceinline__ double hyper_logdet_phi(const DevModel& md, const XVec& x, double lc,
+                                                   double g) {
+  double logdet_phi = hyper_logdet_phi0(md, lc, g);
+  for (int b = 0; b < md.nb; ++b)   // log 10^(2 ecorr_b) per ECORR column of backend b
+    if (md.ec_count[b] > 0.0)
+      logdet_phi += md.ec_count[b] * (2.0 * xget(x, md.ecorr_b[b]) * LN10);
+  return logdet_phi;
+}
+__device__ __forceinline__ double phi_inv_col(const DevModel& md, const XVec& x, int jc, double lc,
+                                              double g, double fsh) {
+  if (jc < md.nf) return exp(-(lc - g * md.lfreq[jc] + md.ldf[jc])) + fsh;
+  const int b = md.ecb[jc - md.nf];
+  int pi = md.ecorr_b[0];
+#pragma unroll
+  for (int j = 1; j < NBMAX; ++j) pi = (b == j) ? md.ecorr_b[j] : pi;
+  return exp(-2.0 * xget(x, pi) * LN10) + fsh;
+}
+// quad, ld: d^T Sigma^-1 d and log|Sigma| over every eliminated column
+__device__ __forceinline__ double hyper_ll(const HyperIn& in, double quad, double ld,
+                                           double logdet_phi) {
+  double ll = -0.5 * (in.logdetN + in.rNr);
+  ll += 0.5 * (quad - ld - logdet_phi);
+  return ll;
+}
+
+// The chain's x and the MH proposal q, in registers (lg_hyper_reg: every lane holds both) ...
+struct XRegs {
+  XVec x, q;
+  __device__ __forceinline__ void copy_in() {
+#pragma unroll
+    for (int j = 0; j < PMAX; ++j) q[j] = x[j];
+  }
+  // v: the step's mhv row (parameter, jump, log u); returns log u
+  __device__ __forceinline__ double propose(const double* v) {
+    const int par = (int)v[0];
+    const double delta = v[1];
+#pragma unroll
+    for (int j = 0; j < PMAX; ++j) q[j] = (j == par) ? x[j] + delta : x[j];
+    return v[2];
+  }
+  __device__ __forceinline__ double lnprior(const DevModel& md) const { return lnpriorP(md, q); }
+  __device__ __forceinline__ void accept() {
+#pragma unroll
+    for (int j = 0; j < PMAX; ++j) x[j] = q[j];
+  }
+  __device__ __forceinline__ bool all_differ(const DevModel& md, double v) const {
+    bool d = true;
+#pragma unroll
+    for (int j = 0; j < PMAX; ++j)
+      if (j < md.P) d = d && (x[j] != v);
+    return d;
+  }
+  __device__ __forceinline__ double get(int i) const { return xget(x, i); }
+};
+// ... or in one wave's LDS, element j read and written by lane j (lg_hyper_ecr, which has no
+// registers to spare); the prior box (lnprior, gibbs.py:337-339) from lane-cached bounds
+struct XLds {
+  double* x;   // [PMAX]
+  double* q;   // [PMAX]
+  int lane, P;
+  double pmin_l, pmax_l;
+  __device__ __forceinline__ void copy_in() {
+    lds_order();
+    if (lane < PMAX) q[lane] = x[lane];
+    lds_order();
+  }
+  __device__ __forceinline__ double propose(const double* v) {
+    lds_order();
+    const int par = (int)v[0];
+    const double delta = v[1];
+    if (lane < PMAX) q[lane] = (lane == par) ? x[lane] + delta : x[lane];
+    const double luacc = v[2];
+    lds_order();
+    return luacc;
+  }
+  __device__ __forceinline__ double lnprior(const DevModel& md) const {
+    const bool out = lane < P && !(q[lane] >= pmin_l && q[lane] <= pmax_l);
+    return __ballot(out) == 0ull ? md.lp_sum : -INFINITY;
+  }
+  __device__ __forceinline__ void accept() {
+    if (lane < PMAX) x[lane] = q[lane];
+  }
+  __device__ __forceinline__ bool all_differ(const DevModel&, double v) const {
+    return __ballot(lane < P && x[lane] == v) == 0ull;
+  }
+  __device__ __forceinline__ double get(int i) const { return x[i]; }
+};
+
+struct HyperOut {
+  bool redraw;   // the sweep draws b (gibbs.py:373)
+  bool Lvalid;   // the kernel holds the factor of Sigma at the final x
+  int fb;        // ... it does not, and refactoring at x failed: the fallback draws b
+  int status;
+  // the b draw's factor is checked against the SVD noise floor (floor_shift)
+  __device__ __forceinline__ bool floor_check(const LArgs& a) const {
+    return !a.floor_pass && redraw && !fb && !(a.st.debug & DEBUG_EXACT_BDRAW);
+  }
+};
+
+// The red-noise MH (gibbs.py:80-111) on state holder xs (XRegs / XLds) with the kernel's
+// lnl(xs, failed) at the proposal xs.q: step -1 evaluates x, steps 0..NHYPER-1 are the
+// proposals (mhv row: parameter, jump, log u), step NHYPER refactors at the final x when the
+// last likelihood was not there.  lead: the chain's thread that writes out_h.  The barrier or
+// fence that orders the kernel's set-up before the first lnl is the caller's.
+template <class X, class LnL>
+__device__ __forceinline__ HyperOut hyper_mh(const DevModel& md, const LArgs& a,
+                                             const HyperIn& in, int c, X& xs, const double* mhv,
+                                             bool lead, LnL&& lnl) {
+  HyperOut o{false, false, 0, in.fail_tm ? 1 : 0};
+  if (!((a.mask & 6u) || a.eval_only)) return o;
+  double l0 = 0.0, p0 = 0.0;
+  // the floor pass refactors the final x only (its MH decisions stand)
+  const int first = ((a.mask & 2u) || a.eval_only) && !a.floor_pass ? -1 : NHYPER;
+  for (int step = first; step <= NHYPER; ++step) {
+    double luacc = 0.0;
+    if (step == NHYPER) {
+      if (a.eval_only || !(a.mask & 4u)) break;
+      // gibbs.py:373: every element of x differs from the sweep's starting last parameter
+      o.redraw = xs.all_differ(md, in.x_last0);
+      if (a.mask & 128u) o.redraw = true;
+      if (!o.redraw || o.Lvalid) break;
+    }
+    if (step < 0 || step == NHYPER) {
+      xs.copy_in();
+    } else {
+      luacc = xs.propose(mhv + 4 * step);
+    }
+    const double p1 = xs.lnprior(md);
+    if (step >= 0 && step < NHYPER && p1 == -INFINITY) continue;
+    int f1 = 0;
+    const double l1 = lnl(xs, f1);
+    if (step == NHYPER) {
+      o.fb = f1;
+      break;
+    }
+    if (f1) o.status |= 1;
+    if (step < 0) {
+      l0 = l1;
+      p0 = p1;
+      // a failed initial factorisation is no factor to draw b from: if every proposal
+      // is then skipped, step NHYPER refactors (and flags status 2) instead
+      o.Lvalid = !f1;
+      if (a.eval_only) {
+        if (lead) a.out_h[c] = l1;
+        break;
+      }
+      continue;
+    }
+    if ((l1 + p1) - (l0 + p0) > luacc) {
+      xs.accept();
+      l0 = l1;
+      p0 = p1;
+      o.Lvalid = true;
+    } else {
+      o.Lvalid = false;
+    }
+  }
+  return o;
+}
+
+// The epilogue (not for eval_only): x, the redraw / fallback / floor flags and the status
+// word, by thread t of the chain; fs: the floor the kernel found (0: none).  Returns whether
+// the kernel draws b now (not the fallback, and with fs > 0 not before the floor pass).
+template <class X>
+__device__ __forceinline__ bool hyper_finish(const DevModel& md, const LArgs& a,
+                                             const HyperIn& in, int c, const X& xs,
+                                             const HyperOut& o, double fs, int t) {
+  if (t < md.P) a.st.x[(size_t)c * md.P + t] = xs.get(t);
+  if (t == 0) {
+    in.sc[SC_REDRAW] = o.redraw ? 1.0 : 0.0;
+    in.sc[SC_FB] = (double)o.fb;
+    if (!a.floor_pass) in.sc[SC_FLOOR] = fs;
+    if (a.st.status)
+      a.st.status[c] = (a.st.status[c] | o.status | ((o.redraw && o.fb) ? 2 : 0) |
+                        (fs > 0.0 ? STATUS_FLOOR : 0)) +
+                       ((fs > 0.0 && !a.floor_pass) ? STATUS_FLOOR_COUNT : 0);
+  }
+  return !(!o.redraw || o.fb || fs > 0.0);
+}
+
+// ------------------------------------------------------------------------------------
+// lg_hyper: red-noise MH on S0 + diag(phi^-1) in LDS; b draw's Fourier block
+// ------------------------------------------------------------------------------------
 
 // MODE 1 (BIG, hyper class 1: blocks past HYPER_LDS_MAX columns): the same MH, likelihood
 // and b draw with the block factored by panel_ldl into the chain's G3 instead of in LDS (S is
@@ -1329,7 +1554,7 @@ __global__ void __launch_bounds__(LBLK) lg_hyper(const DevModel* __restrict__ md
   auto lnl = [&](const XVec& q, int& failed) -> double {
     const double lA = xget(q, md.idx_logA);
     const double g = xget(q, md.idx_gamma);
-    const double lc = 2.0 * lA * 2.302585092994045684 - md.log_12pi2 + (g - 3.0) * md.log_fyr;
+    const double lc = 2.0 * lA * LN10 - md.log_12pi2 + (g - 3.0) * md.log_fyr;
     for (int f = tid; f < nf; f += LBLK) {
       if (f < nfr) {
         ph[f] = exp(-(lc - g * md.lfreq[f] + md.ldf[f])) + fsh;
@@ -1338,13 +1563,13 @@ __global__ void __launch_bounds__(LBLK) lg_hyper(const DevModel* __restrict__ md
         int pi = md.ecorr_b[0];
 #pragma unroll
         for (int j = 1; j < NBMAX; ++j) pi = (b == j) ? md.ecorr_b[j] : pi;
-        ph[f] = exp(-2.0 * xget(q, pi) * 2.302585092994045684) + fsh;
+        ph[f] = exp(-2.0 * xget(q, pi) * LN10) + fsh;
       }
     }
     double logdet_phi = ((double)nfr * lc - g * md.sum_lfreq + md.sum_ldf) + md.logdet_phi_tm;
     for (int b = 0; b < md.nb; ++b)   // log 10^(2 ecorr_b) per ECORR column of backend b
       if (md.ec_count[b] > 0.0)
-        logdet_phi += md.ec_count[b] * (2.0 * xget(q, md.ecorr_b[b]) * 2.302585092994045684);
+        logdet_phi += md.ec_count[b] * (2.0 * xget(q, md.ecorr_b[b]) * LN10);
     __syncthreads();
     double ld = 0.0, quad = 0.0;
     int fl = 0;
@@ -1759,12 +1984,13 @@ __global__ void __launch_bounds__(LBLK) lg_hyper(const DevModel* __restrict__ md
 
 // ------------------------------------------------------------------------------------
 // hyper, register-resident (hyper blocks of at most 62 / 126 columns, MT = 8 / 16): one wave
-// per chain runs lg_hyper's MH with the persistent kernel's elimination (gst_kernel.hpp
+// per chain runs the shared MH (hyper_mh) with the persistent kernel's elimination (gst_kernel.hpp
 // chol_range: 8x8-cyclic register layout, one published column per LDS hand-off) instead of
 // an LDS factorisation with a workgroup barrier per column.  Internal order: the nf hyper
 // columns, unit-prior dummies up to RA (exact no-ops: zero coupling, pivot 1), the augmented
-// row at RA, one zero pad row.  Same variates, MH decisions and outputs (x, status, v's
-// Fourier block, the redraw flags) as lg_hyper; the likelihood sums run in the persistent
+// row at RA, one zero pad row.  The variates, the MH decisions and the outputs (x, status,
+// the redraw flags) come from the code lg_hyper runs (hyper_in, hyper_mh, hyper_finish), v's
+// Fourier block from the same back substitution; the likelihood sums run in the persistent
 // kernel's order.  MT = 16 (config 5's 121-row block, the 80-column ECORR models): 272
 // registers of factor per lane, so no paired tail (its second column view would spill) and
 // two chains per workgroup (S0 is 68 KB of LDS per chain).
@@ -1804,23 +2030,15 @@ __global__ void __launch_bounds__(64 * HR<MT>::WPB) lg_hyper_reg(const DevModel*
   double* mhv = ph + 64 * NCS;
   double* rhs = mhv + 4 * NHYPER;
   const int p = lane >> 3, q = lane & 7;
-  const int nf = md.nf + md.nec, nfr = md.nf, K0 = md.ntm_pad, mp = md.mp;
-  double* sc = a.s.sc + (size_t)c * 16;
-  // floor pass: only the chains whose b draw runs at the SVD noise floor (SC_FLOOR > 0)
-  const double fsh = a.floor_pass ? sc[SC_FLOOR] : 0.0;
-  if (a.floor_pass && !(fsh > 0.0)) return;
+  const int nf = md.nf + md.nec, K0 = md.ntm_pad, mp = md.mp;
+  XRegs xs;
+  load_x(md, a.st, c, xs.x);
+  const HyperIn in = hyper_in(md, a, c, true, lane, mhv);
+  if (in.skip) return;
+  const double fsh = in.fsh;
   const double* Gc = (K0 > 0 ? a.s.G2 : a.s.G) + (size_t)c * mp * mp;
-  const Rng rng = make_rng(a, c);
-  const double* tp = tape_row(a, c);
-  XVec xv;
-  load_x(md, a.st, c, xv);
-  const double logdetN = sc[SC_LOGDETN], rNr = sc[SC_RNR];
-  const double ld_tm = sc[SC_LDTM], quad_tm = sc[SC_QUADTM];
-  const int fail_tm = sc[SC_FAILTM] != 0.0;
-  const double x_last0 = sc[SC_XLAST];
-  int status = fail_tm ? 1 : 0;
-  if (!a.eval_only && !a.floor_pass && lane < NHYPER)
-    mh_variate(md, rng, tp, NWHITE + lane, mhv + 4 * lane);
+  const Rng& rng = in.rng;
+  const double* tp = in.tp;
   // S0 from the Gram's trailing block (lg_tmelim left the Schur complement there), in the
   // cyclic layout: slot (r, s), lane (p, q) = internal (8r+p, 8s+q); diagonal slots hold the
   // full symmetric 8x8 block
@@ -1838,30 +2056,17 @@ __global__ void __launch_bounds__(64 * HR<MT>::WPB) lg_hyper_reg(const DevModel*
     }
   double L[NSL];
   double apr[2] = {1.0, 1.0}, zr[2] = {0.0, 0.0};
-  // factor S0 + diag(phi^-1(q)) in registers; the b-marginalised lnL (gibbs.py:288-329)
-  auto lnl = [&](const XVec& xq, int& failed) __attribute__((always_inline)) -> double {
-    const double lA = xget(xq, md.idx_logA);
+  // factor S0 + diag(phi^-1(q)) in registers; the b-marginalised lnL at the proposal xs.q
+  auto lnl = [&](const XRegs& xs, int& failed) __attribute__((always_inline)) -> double {
+    const XVec& xq = xs.q;
     const double g = xget(xq, md.idx_gamma);
-    const double lc = 2.0 * lA * 2.302585092994045684 - md.log_12pi2 + (g - 3.0) * md.log_fyr;
+    const double lc = hyper_lc(md, xget(xq, md.idx_logA), g);
 #pragma unroll
     for (int cs = 0; cs < NCS; ++cs) {
-      const int jc = 64 * cs + lane;
-      double pv = 0.0;                  // phi^-1 of internal column jc (0: none)
-      if (jc < nfr) {
-        pv = exp(-(lc - g * md.lfreq[jc] + md.ldf[jc])) + fsh;
-      } else if (jc < nf) {
-        const int b = md.ecb[jc - nfr];
-        int pi = md.ecorr_b[0];
-#pragma unroll
-        for (int j = 1; j < NBMAX; ++j) pi = (b == j) ? md.ecorr_b[j] : pi;
-        pv = exp(-2.0 * xget(xq, pi) * 2.302585092994045684) + fsh;
-      }
-      ph[jc] = pv;
+      const int jc = 64 * cs + lane;   // internal column jc's phi^-1 (0: none)
+      ph[jc] = jc < nf ? phi_inv_col(md, xq, jc, lc, g, fsh) : 0.0;
     }
-    double logdet_phi = ((double)nfr * lc - g * md.sum_lfreq + md.sum_ldf) + md.logdet_phi_tm;
-    for (int b = 0; b < md.nb; ++b)
-      if (md.ec_count[b] > 0.0)
-        logdet_phi += md.ec_count[b] * (2.0 * xget(xq, md.ecorr_b[b]) * 2.302585092994045684);
+    const double logdet_phi = hyper_logdet_phi(md, xq, lc, g);
     lds_order();
 #pragma unroll
     for (int r = 0; r < MT; ++r)
@@ -1880,94 +2085,24 @@ __global__ void __launch_bounds__(64 * HR<MT>::WPB) lg_hyper_reg(const DevModel*
       apr[cs] = cc.apr[cs];
       zr[cs] = cc.zr[cs];
     }
-    failed = cc.fail | fail_tm;
+    failed = cc.fail | in.fail_tm;
     if (failed) return -INFINITY;
     const double ld = log(cc.mant) + (double)cc.expo * 0.693147180559945309417;
-    double ll = -0.5 * (logdetN + rNr);
-    ll += 0.5 * ((quad_tm + cc.quad) - (ld_tm + ld) - logdet_phi);
-    return ll;
+    return hyper_ll(in, in.quad_tm + cc.quad, in.ld_tm + ld, logdet_phi);
   };
 
-  const bool run = (a.mask & 6u) || a.eval_only;
-  bool redraw = false, Lvalid = false;
-  int fb = 0;
   lds_order();
-  if (run) {
-    double l0 = 0.0, p0 = 0.0;
-    // the floor pass refactors the final x only (its MH decisions stand)
-    const int first = ((a.mask & 2u) || a.eval_only) && !a.floor_pass ? -1 : NHYPER;
-    for (int step = first; step <= NHYPER; ++step) {
-      XVec xq;
-      double luacc = 0.0;
-      if (step == NHYPER) {
-        if (a.eval_only || !(a.mask & 4u)) break;
-        redraw = true;
-#pragma unroll
-        for (int j = 0; j < PMAX; ++j)
-          if (j < md.P) redraw = redraw && (xv[j] != x_last0);   // gibbs.py:373
-        if (a.mask & 128u) redraw = true;
-        if (!redraw || Lvalid) break;
-      }
-      if (step < 0 || step == NHYPER) {
-#pragma unroll
-        for (int j = 0; j < PMAX; ++j) xq[j] = xv[j];
-      } else {
-        const int par = (int)mhv[4 * step + 0];
-        const double delta = mhv[4 * step + 1];
-#pragma unroll
-        for (int j = 0; j < PMAX; ++j) xq[j] = (j == par) ? xv[j] + delta : xv[j];
-        luacc = mhv[4 * step + 2];
-      }
-      const double p1 = lnpriorP(md, xq);
-      if (step >= 0 && step < NHYPER && p1 == -INFINITY) continue;
-      int f1 = 0;
-      const double l1 = lnl(xq, f1);
-      if (step == NHYPER) {
-        fb = f1;
-        break;
-      }
-      if (f1) status |= 1;
-      if (step < 0) {
-        l0 = l1;
-        p0 = p1;
-        Lvalid = !f1;   // see lg_hyper
-        if (a.eval_only) {
-          if (lane == 0) a.out_h[c] = l1;
-          break;
-        }
-        continue;
-      }
-      if ((l1 + p1) - (l0 + p0) > luacc) {
-#pragma unroll
-        for (int j = 0; j < PMAX; ++j) xv[j] = xq[j];
-        l0 = l1;
-        p0 = p1;
-        Lvalid = true;
-      } else {
-        Lvalid = false;
-      }
-    }
-  }
+  const HyperOut o = hyper_mh(md, a, in, c, xs, mhv, lane == 0, lnl);
   if (a.eval_only) return;
   // the SVD noise floor (floor_shift): pivots of the real columns, timing model and hyper block
   double fs = 0.0;
-  if (!a.floor_pass && redraw && !fb && !(a.st.debug & DEBUG_EXACT_BDRAW)) {
+  if (o.floor_check(a)) {
     double mn, mx;
     const double ap[2] = {apr[0], NCS > 1 ? apr[1] : 1.0};
     pivot_range(ap, lane, 0, 0, nf, mn, mx);
-    fs = floor_of(fmin(mn, sc[SC_TMPMIN]), fmax(mx, sc[SC_TMPMAX]));
+    fs = floor_of(fmin(mn, in.sc[SC_TMPMIN]), fmax(mx, in.sc[SC_TMPMAX]));
   }
-  if (lane < md.P) a.st.x[(size_t)c * md.P + lane] = xget(xv, lane);
-  if (lane == 0) {
-    sc[SC_REDRAW] = redraw ? 1.0 : 0.0;
-    sc[SC_FB] = (double)fb;
-    if (!a.floor_pass) sc[SC_FLOOR] = fs;
-    if (a.st.status)
-      a.st.status[c] = (a.st.status[c] | status | ((redraw && fb) ? 2 : 0) |
-                        (fs > 0.0 ? STATUS_FLOOR : 0)) +
-                       ((fs > 0.0 && !a.floor_pass) ? STATUS_FLOOR_COUNT : 0);
-  }
-  if (!redraw || fb || fs > 0.0) return;   // fs > 0: the floor pass draws b
+  if (!hyper_finish(md, a, in, c, xs, o, fs, lane)) return;
   // b draw, hyper block (lg_hyper's back substitution): the raw factor goes to the S0 region
   // ([slot][lane]: a_ik at 64 SL(i/8, k/8) + 8 (i%8) + k%8); lane owns columns lane + 64 cs
 #pragma unroll
@@ -2092,26 +2227,24 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
   double* mhv = ph + 64;
   double* dx = mhv + 4 * NHYPER;
   double* vx = dx + 64;
-  double* xs = vx + 64;        // [PMAX] x
-  double* xqs = xs + PMAX;     // [PMAX] the proposal being evaluated
+  double* xls = vx + 64;       // [PMAX] x
+  double* xqs = xls + PMAX;    // [PMAX] the proposal being evaluated
   double* phb = xqs + PMAX;    // [NBMAX] phi^-1 (+ f) per backend of the cached elimination
   double* ege = phb + NBMAX;   // [EC_REG_MAX] G_ee of epoch e
   double* ezr = ege + 64 * EC_NEB;   // [EC_REG_MAX] z_e = G_{r,e}
   double* ebd = ezr + 64 * EC_NEB;   // [EC_REG_MAX] the epoch's backend
   const int p = lane >> 3, q = lane & 7;
   const int nfr = md.nf, nec = md.nec, ntm = md.ntm, K0 = md.ntm_pad, mp = md.mp, P = md.P;
-  double* sc = a.s.sc + (size_t)c * 16;
-  const double fsh = a.floor_pass ? sc[SC_FLOOR] : 0.0;
-  if (a.floor_pass && !(fsh > 0.0)) return;
+  // the chain's x and the MH proposal, element j by lane j; the prior box's bounds
+  XLds xs{xls, xqs, lane, P, lane < P ? md.pmin[lane] : 0.0, lane < P ? md.pmax[lane] : 0.0};
+  if (lane < PMAX) xs.x[lane] = lane < P ? a.st.x[(size_t)c * P + lane] : 0.0;
+  // (the timing model is factored with the rest: none of lg_tmelim's terms)
+  const HyperIn in = hyper_in(md, a, c, false, lane, mhv);
+  if (in.skip) return;
+  const double fsh = in.fsh;
   const GDouble* Gg = (const GDouble*)(a.s.G + (size_t)c * mp * mp);   // the raw Gram
-  const Rng rng = make_rng(a, c);
-  const double* tp = tape_row(a, c);
-  if (lane < PMAX) xs[lane] = lane < P ? a.st.x[(size_t)c * P + lane] : 0.0;
-  const double logdetN = sc[SC_LOGDETN], rNr = sc[SC_RNR];
-  const double x_last0 = sc[SC_XLAST];
-  int status = 0;
-  if (!a.eval_only && !a.floor_pass && lane < NHYPER)
-    mh_variate(md, rng, tp, NWHITE + lane, mhv + 4 * lane);
+  const Rng& rng = in.rng;
+  const double* tp = in.tp;
   // internal column of X row i (-1: a unit-prior pad); X rows are internal columns (K0 = 16)
   auto gxi = [&](int i) __attribute__((always_inline)) {
     return (i < ntm || (i >= 16 && i < 16 + nfr)) ? i : (i == RA ? md.raug : -1);
@@ -2146,22 +2279,21 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
   double eck_l = 0.0;
   lds_order();
 
-  // the b-marginalised lnL (gibbs.py:288-329) at the proposal in xqs
-  auto lnl = [&](int& failed) __attribute__((always_inline)) -> double {
-    const double lA = xqs[iA];
-    const double g = xqs[iG];
-    const double lc = 2.0 * lA * 2.302585092994045684 - md.log_12pi2 + (g - 3.0) * md.log_fyr;
+  // the b-marginalised lnL at the proposal xs.q
+  auto lnl = [&](const XLds& xs, int& failed) __attribute__((always_inline)) -> double {
+    const double g = xs.q[iG];
+    const double lc = hyper_lc(md, xs.q[iA], g);
     ph[lane] = (fl_ >= 0 && fl_ < nfr) ? exp(-(lc - g * lf_l + ldf_l)) + fsh : 0.0;
-    double logdet_phi = ((double)nfr * lc - g * md.sum_lfreq + md.sum_ldf) + md.logdet_phi_tm;
-    const double xb = pib >= 0 ? xqs[pib] : 0.0;   // lane b: backend b's log10_ecorr
-    const double tb_ = ecc > 0.0 ? ecc * (2.0 * xb * 2.302585092994045684) : 0.0;
+    double logdet_phi = hyper_logdet_phi0(md, lc, g);
+    const double xb = pib >= 0 ? xs.q[pib] : 0.0;   // lane b: backend b's log10_ecorr
+    const double tb_ = ecc > 0.0 ? ecc * (2.0 * xb * LN10) : 0.0;
 #pragma unroll
     for (int b = 0; b < NBMAX; ++b)   // backend by backend, as lg_hyper<2>
       if (b < nb) logdet_phi += rdlane(tb_, b);
     const bool same = ecvalid && __ballot(pib >= 0 && xb != eck_l) == 0ull;
     CholCtx cc{colq, junk, colq2, lane, p, q, RA, 1.0, 0.0, 0, 0, {1.0, 1.0}, {0.0, 0.0}};
     if (!same) {
-      if (lane < NBMAX) phb[lane] = pib >= 0 ? exp(-2.0 * xb * 2.302585092994045684) + fsh : 0.0;
+      if (lane < NBMAX) phb[lane] = pib >= 0 ? exp(-2.0 * xb * LN10) + fsh : 0.0;
       eck_l = xb;
       // the epochs' coupling rows g_e (lane = X row), two groups of EG in flight
       const int rr = lane >> 3, pp = lane & 7;   // this lane's X row 8 rr + pp
@@ -2297,72 +2429,10 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
     failed = (cc.fail | tm_fail | fle) != 0;
     if (failed) return -INFINITY;
     const double ld = log(cc.mant) + (double)cc.expo * 0.693147180559945309417;
-    double ll = -0.5 * (logdetN + rNr);
-    ll += 0.5 * ((tm_quad + qde + cc.quad) - (tm_ld + lde + ld) - logdet_phi);
-    return ll;
-  };
-  // the proposal in xqs within the prior box (lnprior, gibbs.py:337-339)
-  const double pmin_l = lane < P ? md.pmin[lane] : 0.0, pmax_l = lane < P ? md.pmax[lane] : 0.0;
-  auto in_prior = [&]() __attribute__((always_inline)) {
-    const bool out = lane < P && !(xqs[lane] >= pmin_l && xqs[lane] <= pmax_l);
-    return __ballot(out) == 0ull;
+    return hyper_ll(in, tm_quad + qde + cc.quad, tm_ld + lde + ld, logdet_phi);
   };
 
-  const bool run = (a.mask & 6u) || a.eval_only;
-  bool redraw = false, Lvalid = false;
-  int fb = 0;
-  if (run) {
-    double l0 = 0.0, p0 = 0.0;
-    // the floor pass refactors the final x only (its MH decisions stand)
-    const int first = ((a.mask & 2u) || a.eval_only) && !a.floor_pass ? -1 : NHYPER;
-    for (int step = first; step <= NHYPER; ++step) {
-      double luacc = 0.0;
-      if (step == NHYPER) {
-        if (a.eval_only || !(a.mask & 4u)) break;
-        // gibbs.py:373: every element of x differs from the sweep's starting last parameter
-        redraw = __ballot(lane < P && xs[lane] == x_last0) == 0ull;
-        if (a.mask & 128u) redraw = true;
-        if (!redraw || Lvalid) break;
-      }
-      lds_order();
-      if (step < 0 || step == NHYPER) {
-        if (lane < PMAX) xqs[lane] = xs[lane];
-      } else {
-        const int par = (int)mhv[4 * step + 0];
-        const double delta = mhv[4 * step + 1];
-        if (lane < PMAX) xqs[lane] = (lane == par) ? xs[lane] + delta : xs[lane];
-        luacc = mhv[4 * step + 2];
-      }
-      lds_order();
-      const double p1 = in_prior() ? md.lp_sum : -INFINITY;
-      if (step >= 0 && step < NHYPER && p1 == -INFINITY) continue;
-      int f1 = 0;
-      const double l1 = lnl(f1);
-      if (step == NHYPER) {
-        fb = f1;
-        break;
-      }
-      if (f1) status |= 1;
-      if (step < 0) {
-        l0 = l1;
-        p0 = p1;
-        Lvalid = !f1;   // see lg_hyper
-        if (a.eval_only) {
-          if (lane == 0) a.out_h[c] = l1;
-          break;
-        }
-        continue;
-      }
-      if ((l1 + p1) - (l0 + p0) > luacc) {
-        if (lane < PMAX) xs[lane] = xqs[lane];
-        l0 = l1;
-        p0 = p1;
-        Lvalid = true;
-      } else {
-        Lvalid = false;
-      }
-    }
-  }
+  const HyperOut o = hyper_mh(md, a, in, c, xs, mhv, lane == 0, lnl);
   if (a.eval_only) return;
   lds_order();
   // the SVD noise floor (floor_shift): the epochs' pivots, then X's real columns (timing
@@ -2370,23 +2440,13 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
   double fs = 0.0;
   const double apx = lane < 16 ? tm_apr : f_apr;   // pivot of X column `lane`
   const double zrx = lane < 16 ? tm_zr : f_zr;
-  if (!a.floor_pass && redraw && !fb && !(a.st.debug & DEBUG_EXACT_BDRAW)) {
+  if (o.floor_check(a)) {
     double mn, mx;
     const double ap[2] = {apx, 1.0};
     pivot_range(ap, lane, ntm, 16, 16 + nfr, mn, mx);
     fs = floor_of(fmin(mn, aemin), fmax(mx, aemax));
   }
-  if (lane < P) a.st.x[(size_t)c * P + lane] = xs[lane];
-  if (lane == 0) {
-    sc[SC_REDRAW] = redraw ? 1.0 : 0.0;
-    sc[SC_FB] = (double)fb;
-    if (!a.floor_pass) sc[SC_FLOOR] = fs;
-    if (a.st.status)
-      a.st.status[c] = (a.st.status[c] | status | ((redraw && fb) ? 2 : 0) |
-                        (fs > 0.0 ? STATUS_FLOOR : 0)) +
-                       ((fs > 0.0 && !a.floor_pass) ? STATUS_FLOOR_COUNT : 0);
-  }
-  if (!redraw || fb || fs > 0.0) return;   // fs > 0: the floor pass draws b
+  if (!hyper_finish(md, a, in, c, xs, o, fs, lane)) return;
   // b draw: X's factor -- the timing-model slots in F since the last ECORR elimination (the
   // ECORR values of x), the Fourier block's from the registers -- then the epochs.  Reference
   // order [Fourier | TM | ECORR]: X row i < ntm is b[nf + i], row 16 + f is b[f].

@@ -278,6 +278,25 @@ def test_register_epochs_first_matches_lds_epochs_first(name):
     _compare_large_variants(name, {}, {"epochs_lds": True})
 
 
+def test_wide_register_epochs_first_matches_lds_epochs_first():
+    """lg_hyper_ecr<8,62> (Fourier blocks of 31..46 columns; the fixtures above have 20 and run
+    lg_hyper_ecr<6,46>) against lg_hyper<2>: a multiband pulsar of 80 epochs x 4 sub-band TOAs
+    with 20 components -- 14 timing-model, 40 Fourier and 80 ECORR columns, so X has 55 rows
+    (<= 76), 80 epochs (>= 55) and 120 hyper columns (> 62): hyper class 2, and 16 + 40 = 56
+    X rows past lg_hyper_ecr<6,46>'s 46.  16 chains x 6 sweeps from prior draws, held to
+    _compare_large_variants' tolerances."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a HIP device")
+    psr = data.multiband(nepochs=80, nsub=4, seed=7, components=20)
+    wide = PTA(psr, components=20, efac=(0.2, 10.0), log10_equad=(-10.0, -5.0),
+               log10_A=(-18.0, -12.0), gamma=(0.0, 7.0), log10_ecorr=(-8.0, -5.0), ecorr_dt=30.0)
+    assert (wide.n, wide.m, wide.ntm, wide.nfourier, wide.n_ecorr) == (320, 134, 14, 40, 80)
+    lnl_a, a = _run(wide)
+    lnl_b, b = _run(wide, epochs_lds=True)
+    _assert_lnl_agree(lnl_a, lnl_b, 1)
+    _assert_sweeps_agree(a, b)
+
+
 @pytest.mark.parametrize("name", ["ebig_beta_fixed", "ebig_t_fixed", "mb_beta_fixed",
                                   "mb_t_fixed", "mbn_vvh17_fixed"])
 def test_structured_ecorr_gram_matches_dense_gram(name):
@@ -325,14 +344,25 @@ def _compare_large_variants(name, dbg_a, dbg_b):
         out["status"] = ns.get_state()["status"]
         ns.close()
         outs.append(out)
-    (w1, h1), (w2, h2) = got
+    _assert_lnl_agree(got[0], got[1], C2 // 2 + 1)
+    _assert_sweeps_agree(*outs)
+
+
+def _assert_lnl_agree(lnl_a, lnl_b, min_finite):
+    """(white, hyper) likelihoods of two variants: the white ones bitwise, the b-marginalised
+    ones finite at the same states (at least min_finite of them) and within 1e-10 relative."""
+    (w1, h1), (w2, h2) = ((np.asarray(w), np.asarray(h)) for w, h in (lnl_a, lnl_b))
     np.testing.assert_array_equal(w1, w2)
     ok = np.isfinite(h2)
-    assert ok.sum() > C2 // 2
+    assert ok.sum() >= min_finite
     np.testing.assert_array_equal(np.isfinite(h1), ok)
     r = np.abs(h1[ok] - h2[ok]) / np.abs(h2[ok])
     assert r.max() <= 1e-10, r.max()
-    a, b = outs
+
+
+def _assert_sweeps_agree(a, b):
+    """Recorded sweeps of two variants: no error flags, the same status words and discrete
+    draws, the continuous ones within 1e-8."""
     assert np.all((a["status"] & STATUS_ERRORS) == 0)
     np.testing.assert_array_equal(a["status"], b["status"])
     for k in ("x", "z", "nu"):
