@@ -16,6 +16,8 @@
 #include "gst_kernel.hpp"
 #include "gst_shapes.h"
 #include "gst_large.hpp"
+#include "gst_pack.h"
+#include "gst_plan.h"
 #include "gst_sim.hpp"
 
 namespace {
@@ -40,7 +42,7 @@ struct Ctx {
   std::vector<gst::DevModel> hmd;  // host copies, one per dataset
   gst::DevModel* dmd = nullptr;    // device array [nd] (in allocs)
   int nd = 0, nmax = 0, m = 0, raug = 0;
-  int MT = 0, NS = 0, K0 = 0, WPB = 4;
+  int MT = 0, NS = 0, K0 = 0;
   bool gen = false;                // persistent path: the general white-noise instances
   int ncu = 256;                   // compute units of the device (workgroup sizing)
   double* tmfac = nullptr;         // persistent path: timing-model factor scratch
@@ -58,9 +60,6 @@ struct Ctx {
   // large path: scratch sized for scratch_C chains, per-kernel timing events
   gst::LScratch ls{};
   int scratch_C = 0;
-  size_t lds_tm = 0, lds_hyper = 0, lds_btm = 0, lds_hyper_big = 0, lds_hyper_ec = 0;
-  bool hyper_big = false;          // large path: a hyper block past HYPER_LDS_MAX (G3 scratch)
-  bool hyper_ec = false;           // ... of ECORR epochs, eliminated first (lg_hyper<2>, no G3)
   bool timing = false;
   std::vector<hipEvent_t> evpool;
   std::vector<int> evkind;  // kind of event pair i (events 2i, 2i+1)
@@ -144,7 +143,32 @@ const Shape* shape_for(int nf, int ntm, bool gen = false) {
   return nullptr;
 }
 
-int round_up(int a, int b) { return (a + b - 1) / b * b; }
+using gst::round_up;
+
+// Upload one packed dataset (gst_pack.h) into device buffers owned by cx; md: its DevModel
+// with the pointers set (an empty vector stays a null pointer).
+template <class T>
+int upload_vec(Ctx* cx, const std::vector<T>& v, const T** dev) {
+  void* ptr;
+  if (v.empty()) return 0;
+  if (upload(cx, v.data(), v.size() * sizeof(T), &ptr)) return -1;
+  *dev = (const T*)ptr;
+  return 0;
+}
+int upload_dataset(Ctx* cx, const gst::PackedModel& p, gst::DevModel& md) {
+  md = p.md;
+  return upload_vec(cx, p.Tmf, &md.Tmf) || upload_vec(cx, p.Tcol, &md.Tcol) ||
+         upload_vec(cx, p.resid, &md.resid) || upload_vec(cx, p.sig2, &md.sig2) ||
+         upload_vec(cx, p.lfreq, &md.lfreq) || upload_vec(cx, p.ldf, &md.ldf) ||
+         upload_vec(cx, p.dfA, &md.dfA) || upload_vec(cx, p.dfB, &md.dfB) ||
+         upload_vec(cx, p.ref2int, &md.ref2int) || upload_vec(cx, p.cidx, &md.cidx) ||
+         upload_vec(cx, p.csig2, &md.csig2) || upload_vec(cx, p.ccount, &md.ccount) ||
+         upload_vec(cx, p.Trow, &md.Trow) || upload_vec(cx, p.Gcls, &md.Gcls) ||
+         upload_vec(cx, p.bk, &md.bk) || upload_vec(cx, p.ecb, &md.ecb) ||
+         upload_vec(cx, p.Tx, &md.Tx) || upload_vec(cx, p.Xe, &md.Xe) ||
+         upload_vec(cx, p.ekl, &md.ekl) || upload_vec(cx, p.eblk, &md.eblk)
+             ? -1 : 0;
+}
 
 // gst_debug_variates: the kernel's own samplers, one draw (kind 0, 1) or four (kind 2) per
 // thread, Philox keyed by (seed, chain 0xFFFFFFF0, sweep = call, index, TAG_DEBUG).
@@ -226,351 +250,6 @@ int gst_ctx_destroy(void* ctx) {
   return 0;
 }
 
-// Pack one dataset's constants (shapes already validated) into device buffers owned by cx.
-// ntm_pad / raug: the internal positions of the first Fourier column and of the residual
-// row; a persistent-kernel instance larger than the model leaves unit-prior dummy columns
-// between the Fourier block and the residual row.
-static int pack_dataset(Ctx* cx, const gst_model_desc* d, gst::DevModel& md, int ntm_pad,
-                        int raug, int MT) {
-  const int n = d->n, m = d->m, nf = d->nfourier, ntm = d->ntm, P = d->nparams;
-  const int nec = d->n_ecorr;
-  const int mpad = round_up(raug + 1, 16);
-  const int npad = 64 * ((n + 63) / 64);
-
-  // internal column order: [TM | pad | Fourier | ECORR | r | pad]; reference order
-  // [Fourier | TM | ECORR]
-  std::vector<int> ref2int(m), int2ref(mpad, -1);
-  for (int j = 0; j < nf; ++j) ref2int[j] = ntm_pad + j;
-  for (int j = 0; j < ntm; ++j) ref2int[nf + j] = j;
-  for (int j = 0; j < nec; ++j) ref2int[nf + ntm + j] = ntm_pad + nf + j;
-  for (int j = 0; j < m; ++j) int2ref[ref2int[j]] = j;
-  const int NT = mpad / 16;
-  const int nks = round_up(n, 4) / 4;
-  // k-steps padded with zeros to whole 64-TOA chunks (the large path's Gram stages 16)
-  std::vector<double> Tmf((size_t)(npad / 4) * NT * 64, 0.0);
-  for (int ks = 0; ks < nks; ++ks)
-    for (int X = 0; X < NT; ++X)
-      for (int l = 0; l < 64; ++l) {
-        const int t = 4 * ks + (l >> 4);
-        const int i = 16 * X + (l & 15);
-        double v = 0.0;
-        if (t < n) {
-          if (i == raug)
-            v = d->residuals[t];
-          else if (i < mpad && int2ref[i] >= 0)
-            v = d->T[(size_t)t * m + int2ref[i]];
-        }
-        Tmf[((size_t)ks * NT + X) * 64 + l] = v;
-      }
-  std::vector<double> Tcol((size_t)m * npad, 0.0), resid(npad, 0.0), sig2(npad, 0.0);
-  for (int t = 0; t < n; ++t) {
-    for (int j = 0; j < m; ++j) Tcol[(size_t)j * npad + t] = d->T[(size_t)t * m + j];
-    resid[t] = d->residuals[t];
-    sig2[t] = d->toaerrs[t] * d->toaerrs[t];
-  }
-  // red-noise spectrum pieces: log f_k and log df_k (df from f[::2], enterprise powerlaw)
-  std::vector<double> lf(nf), ldf(nf);
-  for (int k = 0; k < nf; ++k) {
-    lf[k] = std::log(d->ffreqs[k]);
-    const int pair = k / 2;
-    const double prev = pair == 0 ? 0.0 : d->ffreqs[2 * (pair - 1)];
-    ldf[k] = std::log(d->ffreqs[2 * pair] - prev);
-  }
-  // noise classes: TOAs with bit-identical sigma share N0 in the white likelihood
-  // (and equal backend: N0 = efac_b^2 sigma^2 + 10^(2 equad_b) depends on both)
-  std::vector<double> csig2;
-  std::vector<double> ccount;
-  std::vector<int> cback;
-  std::vector<int> cidx(npad, -1);
-  for (int t = 0; t < n; ++t) {
-    const double v = d->toaerrs[t] * d->toaerrs[t];
-    const int bt = (d->nbackend > 1 && d->backend) ? d->backend[t] : 0;
-    int u = 0;
-    while (u < (int)csig2.size() && (csig2[u] != v || cback[u] != bt)) ++u;
-    if (u == (int)csig2.size()) {
-      if (csig2.size() >= 8) break;
-      csig2.push_back(v);
-      ccount.push_back(0.0);
-      cback.push_back(bt);
-    }
-    cidx[t] = u;
-    ccount[u] += 1.0;
-  }
-  int ncls = (int)csig2.size();
-  for (int t = 0; t < n; ++t)
-    if (cidx[t] < 0) ncls = 0;  // more than 8 distinct sigmas: per-TOA path
-  double slf = 0.0, sldf = 0.0;
-  for (int k = 0; k < nf; ++k) {
-    slf += lf[k];
-    sldf += ldf[k];
-  }
-  std::vector<double> dfA(32, 0.0), dfB(32, 0.0);
-  for (int k = 0; k < 30; ++k) {
-    dfA[k] = d->df_A[k];
-    dfB[k] = d->df_B[k];
-  }
-
-  md = gst::DevModel{};
-  void* ptr;
-  if (upload(cx, Tmf.data(), Tmf.size() * 8, &ptr)) return -1;
-  md.Tmf = (const double*)ptr;
-  if (upload(cx, Tcol.data(), Tcol.size() * 8, &ptr)) return -1;
-  md.Tcol = (const double*)ptr;
-  if (upload(cx, resid.data(), resid.size() * 8, &ptr)) return -1;
-  md.resid = (const double*)ptr;
-  if (upload(cx, sig2.data(), sig2.size() * 8, &ptr)) return -1;
-  md.sig2 = (const double*)ptr;
-  if (upload(cx, lf.data(), lf.size() * 8, &ptr)) return -1;
-  md.lfreq = (const double*)ptr;
-  if (upload(cx, ldf.data(), ldf.size() * 8, &ptr)) return -1;
-  md.ldf = (const double*)ptr;
-  if (upload(cx, dfA.data(), dfA.size() * 8, &ptr)) return -1;
-  md.dfA = (const double*)ptr;
-  if (upload(cx, dfB.data(), dfB.size() * 8, &ptr)) return -1;
-  md.dfB = (const double*)ptr;
-  if (upload(cx, ref2int.data(), ref2int.size() * sizeof(int), &ptr)) return -1;
-  md.ref2int = (const int*)ptr;
-  md.ncls = ncls;
-  for (int u = 0; u < 8; ++u) md.cls_b[u] = u < ncls ? cback[u] : 0;
-  if (ncls > 0) {
-    if (upload(cx, cidx.data(), cidx.size() * sizeof(int), &ptr)) return -1;
-    md.cidx = (const int*)ptr;
-    if (upload(cx, csig2.data(), csig2.size() * 8, &ptr)) return -1;
-    md.csig2 = (const double*)ptr;
-    if (upload(cx, ccount.data(), ccount.size() * 8, &ptr)) return -1;
-    md.ccount = (const double*)ptr;
-  }
-  md.sum_lfreq = slf;
-  md.sum_ldf = sldf;
-  // Persistent kernel, <= 8 noise classes: the Gram of the augmented basis per
-  // class, G_k = sum_{t in class k} [T|r]_t [T|r]_t^T (long double, rounded once), in the
-  // kernel's 8x8-cyclic register layout [k][slot][lane], and the augmented rows
-  // [T|r]_t in internal order, stored [t][i % 8][i / 8] (a lane's row entries 8 r + p,
-  // r = 0 .. MT-1, are contiguous: 128-bit loads).  With them a sweep's Gram T^T N^-1 [T|r] is
-  //   sum_k c_k G_k + sum_{t: z_t = 1} c_k(t) (1 / alpha_t - 1) [T|r]_t [T|r]_t^T,
-  // c_k = 1 / (efac_b^2 sigma_k^2 + 10^(2 equad_b)): N_t = alpha_t^z_t N0_k(t) (gibbs.py:154,
-  // 297-304), a rank-(outlier count) update instead of the n-TOA MFMA Gram (gst_kernel.hpp
-  // gram_and_tm; the kernel takes it while at most LR_MAX TOAs are flagged).
-  md.Gcls = nullptr;
-  md.Trow = nullptr;
-  if (MT > 0 && ncls > 0) {
-    const int W = 8 * MT, NSL = MT * (MT + 1) / 2;
-    std::vector<double> trow((size_t)npad * W, 0.0);
-    for (int t = 0; t < n; ++t)
-      for (int i = 0; i < W; ++i) {
-        double v = 0.0;
-        if (i == raug)
-          v = d->residuals[t];
-        else if (i < mpad && int2ref[i] >= 0)
-          v = d->T[(size_t)t * m + int2ref[i]];
-        trow[(size_t)t * W + (i & 7) * MT + (i >> 3)] = v;   // [t][i % 8][i / 8]
-      }
-    std::vector<long double> acc((size_t)ncls * W * W, 0.0L);
-    for (int t = 0; t < n; ++t) {
-      long double* a = acc.data() + (size_t)cidx[t] * W * W;
-      const double* row = trow.data() + (size_t)t * W;
-      auto at = [&](int i) { return row[(i & 7) * MT + (i >> 3)]; };
-      for (int i = 0; i < W; ++i) {
-        const double ri = at(i);
-        if (ri == 0.0) continue;
-        for (int j = 0; j <= i; ++j) a[(size_t)i * W + j] += (long double)ri * at(j);
-      }
-    }
-    std::vector<double> gcls((size_t)ncls * NSL * 64, 0.0);
-    for (int k = 0; k < ncls; ++k)
-      for (int r = 0; r < MT; ++r)
-        for (int sl = 0; sl <= r; ++sl)
-          for (int l = 0; l < 64; ++l) {
-            const int i = 8 * r + (l >> 3), j = 8 * sl + (l & 7);
-            const long double v = i >= j ? acc[((size_t)k * W + i) * W + j]
-                                         : acc[((size_t)k * W + j) * W + i];
-            gcls[((size_t)k * NSL + gst::SL(r, sl)) * 64 + l] = (double)v;
-          }
-    if (upload(cx, trow.data(), trow.size() * 8, &ptr)) return -1;
-    md.Trow = (const double*)ptr;
-    if (upload(cx, gcls.data(), gcls.size() * 8, &ptr)) return -1;
-    md.Gcls = (const double*)ptr;
-  }
-
-  md.n = n;
-  md.m = m;
-  md.mp = mpad;
-  md.nf = nf;
-  md.ntm = ntm;
-  md.ntm_pad = ntm_pad;
-  md.raug = raug;
-  md.nks = nks;
-  md.npad = npad;
-  md.nslot_toa = npad / 64;
-  md.P = P;
-  md.idx_efac = d->idx_efac;
-  md.idx_equad = d->idx_equad;
-  md.idx_logA = d->idx_log10_A;
-  md.idx_gamma = d->idx_gamma;
-  md.efac_const = d->efac_const;
-  for (int j = 0; j < gst::PMAX; ++j) {
-    md.pmin[j] = j < P ? d->pmin[j] : 0.0;
-    md.pmax[j] = j < P ? d->pmax[j] : 0.0;
-    md.lp_in[j] = j < P ? -std::log(d->pmax[j] - d->pmin[j]) : 0.0;
-    md.hind[j] = j < d->n_hyper ? d->hyper_idx[j] : d->hyper_idx[0];
-    md.wind[j] = j < d->n_white ? d->white_idx[j] : d->white_idx[0];
-  }
-  // general white noise: per-backend parameter indices, per-TOA backend, ECORR columns
-  const int nb = d->nbackend > 0 ? d->nbackend : 1;
-  md.nb = nb;
-  for (int b = 0; b < gst::NBMAX; ++b) {
-    md.efac_b[b] = b < nb ? (d->efac_idx ? d->efac_idx[b] : d->idx_efac) : -1;
-    md.equad_b[b] = b < nb ? (d->equad_idx ? d->equad_idx[b] : d->idx_equad) : d->idx_equad;
-    md.ecorr_b[b] = b < nb && d->ecorr_idx ? d->ecorr_idx[b] : -1;
-    md.ec_count[b] = 0.0;
-  }
-  md.nec = nec;
-  md.bk = nullptr;
-  md.ecb = nullptr;
-  if (nb > 1) {
-    std::vector<int> bk(npad, 0);
-    for (int t = 0; t < n; ++t) bk[t] = d->backend ? d->backend[t] : 0;
-    if (upload(cx, bk.data(), bk.size() * sizeof(int), &ptr)) return -1;
-    md.bk = (const int*)ptr;
-  }
-  if (nec > 0) {
-    std::vector<int> eb(nec);
-    for (int e = 0; e < nec; ++e) {
-      eb[e] = d->ecorr_backend ? d->ecorr_backend[e] : 0;
-      md.ec_count[eb[e]] += 1.0;
-    }
-    if (upload(cx, eb.data(), eb.size() * sizeof(int), &ptr)) return -1;
-    md.ecb = (const int*)ptr;
-  }
-  // large path, disjoint ECORR epochs: the structured Gram's operands (gst_large.hpp
-  // lg_gram_ec), when [timing model | Fourier | r | 1] fits four 16-column tiles
-  md.Tx = md.Xe = nullptr;
-  md.ekl = md.eblk = nullptr;
-  md.gx_nt = md.nkse = md.neblk = 0;
-  const int Q = ntm_pad + nf;
-  bool ec_disj = MT == 0 && nec > 0;
-  for (int t = 0; ec_disj && t < n; ++t) {
-    int nz = 0;
-    for (int e = 0; e < nec; ++e) nz += d->T[(size_t)t * m + nf + ntm + e] != 0.0;
-    ec_disj = nz <= 1;
-  }
-  if (ec_disj && Q + 2 <= 64) {
-    const int NX = (Q + 2 + 15) / 16;
-    // compact [X | r | 1] row q of TOA t (the ones column stays zero here: lg_gram_ec's G_xx
-    // does not use it)
-    auto xval = [&](int t, int q) -> double {
-      if (q < Q) return int2ref[q] >= 0 ? d->T[(size_t)t * m + int2ref[q]] : 0.0;
-      return q == Q ? d->residuals[t] : 0.0;
-    };
-    std::vector<double> tx((size_t)(npad / 4) * NX * 64, 0.0);
-    for (int ks = 0; ks < nks; ++ks)
-      for (int X = 0; X < NX; ++X)
-        for (int l = 0; l < 64; ++l) {
-          const int t = 4 * ks + (l >> 4);
-          if (t < n) tx[((size_t)ks * NX + X) * 64 + l] = xval(t, 16 * X + (l & 15));
-        }
-    // the epochs' TOAs (ascending), 16 epochs per block, each block padded to whole k-steps
-    std::vector<std::vector<int>> etoa(nec);
-    for (int t = 0; t < n; ++t)
-      for (int e = 0; e < nec; ++e)
-        if (d->T[(size_t)t * m + nf + ntm + e] != 0.0) etoa[e].push_back(t);
-    const int neblk = (nec + 15) / 16;
-    std::vector<int> eblk(neblk + 1, 0), ent_t, ent_e;
-    for (int b = 0; b < neblk; ++b) {
-      eblk[b] = (int)ent_t.size() / 4;
-      for (int e = 16 * b; e < std::min(nec, 16 * b + 16); ++e)
-        for (int t : etoa[e]) {
-          ent_t.push_back(t);
-          ent_e.push_back(e - 16 * b);
-        }
-      while (ent_t.size() % 4) {
-        ent_t.push_back(-1);
-        ent_e.push_back(-1);
-      }
-    }
-    eblk[neblk] = (int)ent_t.size() / 4;
-    const int nkse = std::max(16, round_up(eblk[neblk], 16));
-    ent_t.resize((size_t)nkse * 4, -1);
-    ent_e.resize((size_t)nkse * 4, -1);
-    std::vector<double> xe((size_t)nkse * NX * 64, 0.0);
-    std::vector<int> ekl((size_t)nkse * 8, -1);
-    for (int p = 0; p < 4 * nkse; ++p) {
-      ekl[2 * p] = ent_t[p];
-      ekl[2 * p + 1] = ent_e[p];
-    }
-    for (int b = 0; b < neblk; ++b)
-      for (int p = 4 * eblk[b]; p < 4 * eblk[b + 1]; ++p) {
-        const int t = ent_t[p];
-        if (t < 0) continue;
-        const int e = 16 * b + ent_e[p];
-        const double u = d->T[(size_t)t * m + nf + ntm + e];
-        const int ks = p / 4, k = p % 4;
-        for (int X = 0; X < NX; ++X)
-          for (int j = 0; j < 16; ++j) {
-            const int q = 16 * X + j;
-            const double v = q == Q + 1 ? u * u : u * xval(t, q);
-            xe[((size_t)ks * NX + X) * 64 + 16 * k + j] = v;
-          }
-      }
-    if (upload(cx, tx.data(), tx.size() * 8, &ptr)) return -1;
-    md.Tx = (const double*)ptr;
-    if (upload(cx, xe.data(), xe.size() * 8, &ptr)) return -1;
-    md.Xe = (const double*)ptr;
-    if (upload(cx, ekl.data(), ekl.size() * sizeof(int), &ptr)) return -1;
-    md.ekl = (const int*)ptr;
-    if (upload(cx, eblk.data(), eblk.size() * sizeof(int), &ptr)) return -1;
-    md.eblk = (const int*)ptr;
-    md.gx_nt = NX;
-    md.nkse = nkse;
-    md.neblk = neblk;
-  }
-  md.lp_sum = 0.0;  // Python sum() order (gibbs.py:339)
-  for (int j = 0; j < P; ++j) md.lp_sum += md.lp_in[j];
-  md.nh = d->n_hyper;
-  md.nw = d->n_white;
-  md.sig_h = 0.05 * d->n_hyper;
-  md.sig_w = 0.05 * d->n_white;
-  const double probs[5] = {0.1, 0.15, 0.5, 0.15, 0.1};
-  const double sizes[5] = {0.1, 0.5, 1.0, 3.0, 10.0};
-  double cs = 0.0, cdf[5];
-  for (int i = 0; i < 5; ++i) {
-    cs += probs[i];
-    cdf[i] = cs;
-  }
-  for (int i = 0; i < 5; ++i) {
-    md.mh_cdf[i] = cdf[i] / cdf[4];
-    md.mh_size[i] = sizes[i];
-  }
-  md.model = d->model;
-  md.vary_df = d->vary_df;
-  md.vary_alpha = d->vary_alpha;
-  if (d->theta_prior_beta) {
-    md.mk = n * d->mprior;
-    md.k1mm = n * (1.0 - d->mprior);
-  } else {
-    md.mk = 1.0;
-    md.k1mm = 1.0;
-  }
-  md.pspin = d->pspin;
-  md.tm_phiinv = 1.0 / d->tm_weight;
-  md.logdet_phi_tm = ntm * std::log(d->tm_weight);
-  md.log_fyr = std::log(1.0 / (365.25 * 86400.0));
-  md.log_12pi2 = std::log(12.0) + 2.0 * std::log(M_PI);
-  return 0;
-}
-
-// ECORR epochs are disjoint when no TOA has a nonzero entry in two of the last n_ecorr
-// columns of T (lg_hyper<2>'s elimination takes the ECORR block of T^T N^-1 T as diagonal)
-static bool ecorr_disjoint(const gst_model_desc* d) {
-  const int m = d->m, nec = d->n_ecorr;
-  for (int t = 0; t < d->n; ++t) {
-    int nz = 0;
-    for (int j = m - nec; j < m; ++j) nz += d->T[(size_t)t * m + j] != 0.0;
-    if (nz > 1) return false;
-  }
-  return true;
-}
-
 static int check_desc(const gst_model_desc* d) {
   const int n = d->n, m = d->m, nf = d->nfourier, ntm = d->ntm, P = d->nparams;
   const int nec = d->n_ecorr, nb = d->nbackend > 0 ? d->nbackend : 1;
@@ -635,6 +314,7 @@ int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
   Ctx* cx = static_cast<Ctx*>(ctx);
   if (!cx || !descs || nd <= 0) return fail("gst_model_set_batch: null argument");
   HIP_OK(hipSetDevice(cx->device));
+  // 1. validate
   int nmax = 0;
   for (int i = 0; i < nd; ++i) {
     if (check_desc(&descs[i])) return -1;
@@ -643,10 +323,11 @@ int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
                   "index sets (dataset " + std::to_string(i) + ")");
     nmax = std::max(nmax, descs[i].n);
   }
+  // 2. shape and path
   const gst_model_desc* d = &descs[0];
   const int nf = d->nfourier, ntm = d->ntm, m = d->m, nec = d->n_ecorr;
   bool disjoint = true;   // the batch's datasets all: one hyper class per batch structure
-  for (int i = 0; i < nd && nec > 0; ++i) disjoint = disjoint && ecorr_disjoint(&descs[i]);
+  for (int i = 0; i < nd && nec > 0; ++i) disjoint = disjoint && gst::ecorr_disjoint(&descs[i]);
   const bool gen = !classic(d) && general_fits(d);
   const Shape* sh = shape_for(nf + (gen ? nec : 0), ntm, gen);
   const int MT = sh ? sh->MT : 0, K0 = sh ? sh->K0 : 0;
@@ -673,35 +354,35 @@ int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
                   K0, raug, gen ? 1 : 0, nmax, m, nf, ntm, nec);
     return fail(b);
   }
-  if (path == GST_PATH_LARGE) {
-    // hyper blocks past HYPER_LDS_MAX columns: ECORR epochs around a small timing-model +
-    // Fourier block are eliminated first (lg_hyper<2>), other blocks are factored in global
-    // memory (lg_hyper<1>), whose LDS holds a 16-column panel of all mp rows plus three vectors
-    const int ms = nf + nec + 1, mpl = round_up(round_up(ntm > 0 ? ntm : 1, 16) + nf + nec + 1, 16);
-    const int hc = gst::hyper_class(nf + nec, 0, nec, ntm + nf + 1, disjoint ? 1 : 0), qx = ntm + nf + 1;
-    if (hc == 1 &&
-        (size_t)(mpl * (gst::TM_PW + 1) + gst::TM_PW + nf + nec + 2 * ms) * 8 > 160 * 1024)
-      return fail("gst_model_set: large path: basis too large for the LDS panel of the "
-                  "red-noise / ECORR block elimination");
-    // lg_hyper<2> (ECORR epochs eliminated first): its LDS vectors span the basis
-    if (hc == 2 && (size_t)(2 * qx * (qx + 1) + nf + 2 * nec + 4 * mpl +
-                            2 * gst::EC_ECH * (round_up(qx, 16) + 1)) * 8 > 160 * 1024)
-      return fail("gst_model_set: large path: too many ECORR epochs for the LDS of their "
-                  "elimination");
-  }
-  free_model(cx);
+  const bool large = path == GST_PATH_LARGE;
   // large path: timing-model block padded to whole 16-column MFMA tiles, no dummies
-  const int ntm_pad = path == GST_PATH_LARGE ? round_up(ntm > 0 ? ntm : 1, 16) : 8 * K0;
-  const int raug_pack = path == GST_PATH_LARGE ? ntm_pad + nf + nec : raug;
+  const int ntm_pad = large ? round_up(ntm > 0 ? ntm : 1, 16) : 8 * K0;
+  const int raug_pack = large ? ntm_pad + nf + nec : raug;
+  // 3. large path: the LDS layouts of its kernels (gst_plan.h), from the descriptor's
+  // integers.  Hyper blocks past HYPER_LDS_MAX columns: ECORR epochs around a small
+  // timing-model + Fourier block are eliminated first (lg_hyper<2>), other blocks are factored
+  // in global memory (lg_hyper<1>), whose LDS holds a 16-column panel of all mp rows
+  const int mpl = round_up(raug_pack + 1, 16);
+  const size_t limit = gst::LDS_LIMIT;
+  const size_t lds_h0 = (size_t)gst::HyperLds<0>(nf, nec, ntm, mpl).total * 8;
+  const size_t lds_h1 = (size_t)gst::HyperLds<1>(nf, nec, ntm, mpl).total * 8;
+  const size_t lds_h2 = (size_t)gst::HyperLds<2>(nf, nec, ntm, mpl).total * 8;
+  const int hc = gst::hyper_class(nf + nec, 0, nec, ntm + nf + 1, disjoint ? 1 : 0);
+  if (large && hc == 1 && lds_h1 > limit)
+    return fail("gst_model_set: large path: basis too large for the LDS panel of the "
+                "red-noise / ECORR block elimination");
+  if (large && hc == 2 && lds_h2 > limit)   // its LDS vectors span the basis
+    return fail("gst_model_set: large path: too many ECORR epochs for the LDS of their "
+                "elimination");
+  // 4. pack and upload
+  free_model(cx);
   std::vector<gst::DevModel> hmd(nd);
-  for (int i = 0; i < nd; ++i) {
-    if (pack_dataset(cx, &descs[i], hmd[i], ntm_pad, raug_pack,
-                     path == GST_PATH_PERSISTENT ? MT : 0)) {
+  for (int i = 0; i < nd; ++i)
+    if (upload_dataset(cx, gst::pack_dataset(&descs[i], ntm_pad, raug_pack, large ? 0 : MT, disjoint),
+                       hmd[i])) {
       free_model(cx);
       return -1;
     }
-    hmd[i].ec_disjoint = disjoint ? 1 : 0;
-  }
   void* ptr;
   if (upload(cx, hmd.data(), hmd.size() * sizeof(gst::DevModel), &ptr)) return -1;
   cx->dmd = (gst::DevModel*)ptr;
@@ -711,52 +392,28 @@ int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
   cx->MT = MT;
   cx->NS = NS;
   cx->K0 = K0;
-  cx->raug = raug;
+  cx->raug = raug_pack;
   cx->m = m;
-  cx->WPB = 4;
-  cx->gen = path == GST_PATH_PERSISTENT && gen;
+  cx->gen = !large && gen;
   cx->path = path;
-  cx->hyper_big = cx->hyper_ec = false;
-  if (path == GST_PATH_LARGE) {
-    const gst::DevModel& h = hmd[0];
-    cx->raug = h.raug;
-    cx->lds_tm = (size_t)h.mp * (gst::TM_PW + 1) * 8;
-    const int ms = h.nf + h.nec + 1;
-    const int hc = gst::hyper_class_of(h, 0);
-    // lg_hyper<1> runs for class 1, and for class 2 under GST_DEBUG_LARGE_HYPER (its G3
-    // scratch is then allocated at the first such launch)
-    cx->hyper_big = gst::hyper_class_of(h, 1) == 1;
-    cx->hyper_ec = hc == 2;
-    const bool lds_fits = h.nf + h.nec <= gst::HYPER_LDS_MAX;   // lg_hyper<0> (also forced)
-    cx->lds_hyper = lds_fits ? (size_t)(ms * (ms + 1) + h.nf + h.nec + 2 * ms) * 8 : 0;
-    cx->lds_hyper_big = (size_t)(h.mp * (gst::TM_PW + 1) + gst::TM_PW + h.nf + h.nec + 2 * ms) * 8;
-    // lg_hyper<2>: X and XB [qx][qx + 1], phi^-1 [nf + nec], four vectors of mp, a_e [nec],
-    // two chunks of couplings [EC_ECH][qxp] and their 1 / a_e
-    const int qx = h.ntm + h.nf + 1, qxp = round_up(qx, 16);
-    cx->lds_hyper_ec = (size_t)(2 * qx * (qx + 1) + h.nf + h.nec + 4 * h.mp + h.nec +
-                                2 * gst::EC_ECH * qxp + 2 * gst::EC_ECH) * 8;
-    cx->lds_btm = (size_t)(3 * h.ntm_pad + h.raug) * 8;
-    HIP_OK(hipFuncSetAttribute((const void*)gst::lg_gram,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, gst::GRAM_LDS * 8));
-    HIP_OK(hipFuncSetAttribute((const void*)gst::lg_tmelim,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)cx->lds_tm));
-    if (cx->hyper_big && cx->lds_hyper_big <= 160 * 1024)
-      HIP_OK(hipFuncSetAttribute((const void*)gst::lg_hyper<1>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)cx->lds_hyper_big));
-    if (hc == 2)
-      HIP_OK(hipFuncSetAttribute((const void*)gst::lg_hyper<2>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)cx->lds_hyper_ec));
-    if (lds_fits)
-      HIP_OK(hipFuncSetAttribute((const void*)gst::lg_hyper<0>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)cx->lds_hyper));
-    HIP_OK(hipFuncSetAttribute((const void*)gst::lg_btm,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)cx->lds_btm));
+  if (large) {
+    auto set_lds = [](const void* kern, size_t bytes) {
+      return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    };
+    HIP_OK(set_lds((const void*)gst::lg_gram, gst::GRAM_LDS * 8));
+    HIP_OK(set_lds((const void*)gst::lg_tmelim, (size_t)gst::TmelimLds(mpl).total * 8));
+    HIP_OK(set_lds((const void*)gst::lg_btm, (size_t)gst::BtmLds(ntm_pad, raug_pack).total * 8));
+    // lg_hyper<0>: class 0, and smaller blocks under GST_DEBUG_LARGE_HYPER; lg_hyper<1>: class
+    // 1, and class 2 under GST_DEBUG_LARGE_HYPER when its panel fits (plan_large refuses else)
+    if (nf + nec <= gst::HYPER_LDS_MAX) HIP_OK(set_lds((const void*)gst::lg_hyper<0>, lds_h0));
+    if (nf + nec > gst::HYPER_LDS_MAX && lds_h1 <= limit)
+      HIP_OK(set_lds((const void*)gst::lg_hyper<1>, lds_h1));
+    if (hc == 2) HIP_OK(set_lds((const void*)gst::lg_hyper<2>, lds_h2));
   }
   cx->has_model = true;
   return 0;
 }
+
 
 int gst_model_set(void* ctx, const gst_model_desc* d) { return gst_model_set_batch(ctx, d, 1); }
 
@@ -790,24 +447,9 @@ static int ev_mark(Ctx* cx, int kind, hipStream_t st, bool begin) {
   return 0;
 }
 
-#define LG_LAUNCH(kind, kern, grid, block, lds)                                  \
-  do {                                                                           \
-    if (ev_mark(cx, kind, st, true)) return -1;                                  \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, cx->dmd, a);                  \
-    HIP_OK(hipGetLastError());                                                   \
-    if (ev_mark(cx, kind, st, false)) return -1;                                 \
-  } while (0)
-
-// per-TOA scratch row stride of the large path: the batch's largest npad
-static int large_ys(const Ctx* cx) {
-  int ys = 0;
-  for (const gst::DevModel& h : cx->hmd) ys = std::max(ys, h.npad);
-  return ys;
-}
-
-static int ensure_scratch(Ctx* cx, int C, hipStream_t st) {
-  // lg_hyper<1>'s G3: class-1 models, and class-2 ones under GST_DEBUG_LARGE_HYPER
-  const bool need_g3 = cx->hyper_big && (!cx->hyper_ec || (cx->debug & GST_DEBUG_LARGE_HYPER));
+// npad: the per-TOA scratch row stride (the batch's largest npad); need_g3: lg_hyper<1> runs
+// (class-1 models, and class-2 ones under GST_DEBUG_LARGE_HYPER)
+static int ensure_scratch(Ctx* cx, int C, size_t npad, bool need_g3, hipStream_t st) {
   if (C <= cx->scratch_C && (!need_g3 || cx->ls.G3)) return 0;
   if (C <= cx->scratch_C) {
     const size_t mp = cx->hmd[0].mp;
@@ -817,7 +459,7 @@ static int ensure_scratch(Ctx* cx, int C, hipStream_t st) {
   }
   free_scratch(cx, st);
   const gst::DevModel& h = cx->hmd[0];
-  const size_t mp = h.mp, npad = large_ys(cx);
+  const size_t mp = h.mp;
   HIP_OK(hipMallocAsync((void**)&cx->ls.G, (size_t)C * mp * mp * 8, st));
   HIP_OK(hipMallocAsync((void**)&cx->ls.G2, (size_t)C * mp * mp * 8, st));
   HIP_OK(hipMallocAsync((void**)&cx->ls.y, (size_t)C * npad * 8, st));
@@ -836,181 +478,60 @@ static int ensure_scratch(Ctx* cx, int C, hipStream_t st) {
   return 0;
 }
 
-// The red-noise MH block's launches: one per hyper kernel class present (gst_large.hpp
-// hyper_class); a chain of another class returns at once.
-static int launch_hyper(Ctx* cx, gst::LArgs& a, const bool (&hcls)[7], dim3 g8, dim3 b8,
-                        dim3 g16, dim3 b16, dim3 g_chain, dim3 b_chain, hipStream_t st) {
-  if (hcls[0]) {
-    a.kclass = 8;
-    LG_LAUNCH(GST_K_HYPER, gst::lg_hyper_reg<8>, g8, b8, 0);
-  }
-  if (hcls[1]) {
-    a.kclass = 16;
-    LG_LAUNCH(GST_K_HYPER, gst::lg_hyper_reg<16>, g16, b16, 0);
-  }
-  if (hcls[2]) {
-    a.kclass = 0;
-    LG_LAUNCH(GST_K_HYPER, gst::lg_hyper<0>, g_chain, b_chain, cx->lds_hyper);
-  }
-  if (hcls[3]) {
-    // (a class-2 model forced here by GST_DEBUG_LARGE_HYPER may have a block whose panel
-    // does not fit the LDS: refuse it rather than fail at launch)
-    if (cx->lds_hyper_big > 160 * 1024)
-      return fail("gst: GST_DEBUG_LARGE_HYPER: this model's red-noise / ECORR block is too "
-                  "large for the blocked elimination's LDS panel (lg_hyper<1>)");
-    a.kclass = 1;
-    LG_LAUNCH(GST_K_HYPER, gst::lg_hyper<1>, g_chain, b_chain, cx->lds_hyper_big);
-  }
-  if (hcls[4]) {
-    a.kclass = 2;
-    LG_LAUNCH(GST_K_HYPER, gst::lg_hyper<2>, g_chain, b_chain, cx->lds_hyper_ec);
-  }
-  // class 2 on one wave per chain (lg_hyper_ecr<MT, RA>, gst_large.hpp ec_reg_mt)
-  if (hcls[5]) {
-    a.kclass = 2;
-    const int w = gst::HE<6, 46>::WPB;
-    const auto kern = &gst::lg_hyper_ecr<6, 46>;
-    LG_LAUNCH(GST_K_HYPER, kern, dim3((a.C + w - 1) / w), dim3(64 * w), 0);
-  }
-  if (hcls[6]) {
-    a.kclass = 2;
-    const int w = gst::HE<8, 62>::WPB;
-    const auto kern = &gst::lg_hyper_ecr<8, 62>;
-    LG_LAUNCH(GST_K_HYPER, kern, dim3((a.C + w - 1) / w), dim3(64 * w), 0);
-  }
+// The large path's kernels by id (gst_plan.h LargeKernel); lg_gram takes two more arguments
+using lkfn_t = void (*)(const gst::DevModel*, gst::LArgs);
+static const lkfn_t kLargeKernels[gst::LK_COUNT] = {
+    gst::lg_tb, gst::lg_record,
+    gst::lg_white<gst::TBLK_WAVE>, gst::lg_white<gst::TBLK_SMALL>, gst::lg_white<gst::TBLK>,
+    gst::lg_gram_ec<1>, gst::lg_gram_ec<2>, gst::lg_gram_ec<3>, gst::lg_gram_ec<4>,
+    gst::lg_gram_small<1>, gst::lg_gram_small<2>, gst::lg_gram_small<3>, gst::lg_gram_small<4>,
+    gst::lg_gram_small<5>, gst::lg_gram_small<6>, nullptr /* lg_gram */,
+    gst::lg_tmelim,
+    gst::lg_hyper_reg<8>, gst::lg_hyper_reg<16>, gst::lg_hyper<0>, gst::lg_hyper<1>,
+    gst::lg_hyper<2>, gst::lg_hyper_ecr<6, 46>, gst::lg_hyper_ecr<8, 62>,
+    gst::lg_btm,
+    gst::lg_toa<gst::TBLK_SMALL>, gst::lg_toa<gst::TBLK>};
+
+static int run_launch(Ctx* cx, const gst::LargePlan& p, const gst::Launch& l, gst::LArgs& a,
+                      hipStream_t st) {
+  if (l.kclass >= 0) a.kclass = l.kclass;
+  a.floor_pass = l.floor_pass;
+  if ((l.ev & gst::EV_BEGIN) && ev_mark(cx, l.kind, st, true)) return -1;
+  const dim3 grid(l.gx, l.gy), block(l.block);
+  if (l.kernel == gst::LK_GRAM)
+    hipLaunchKernelGGL(gst::lg_gram, grid, block, l.lds, st, cx->dmd, a, p.nsb, p.npairs);
+  else
+    hipLaunchKernelGGL(kLargeKernels[l.kernel], grid, block, l.lds, st, cx->dmd, a);
+  HIP_OK(hipGetLastError());
+  if ((l.ev & gst::EV_END) && ev_mark(cx, l.kind, st, false)) return -1;
+  // one count per chain per Gram stage (gst_gram_counts)
+  if ((l.ev & gst::EV_END) && l.kind == GST_K_GRAM && !a.eval_only)
+    cx->gram_large += (unsigned long long)a.C;
   return 0;
 }
 
-// One sweep = record, white, gram, tmelim, hyper, btm, tb, toa launches (gst_large.hpp).
+// The plan (gst_plan.h plan_large) is built once per call; its sweep list runs nsweeps times.
 static int launch_large(Ctx* cx, const gst::DevState& ds, const gst::DevRec& dr,
                         const gst::DevTape& dt, int C, int nsweeps, long long sweep0,
                         int record_every, unsigned mask, unsigned long long seed,
                         long long chain0, int eval_only, double* ow, double* oh,
                         hipStream_t st) {
-  if (ensure_scratch(cx, C, st)) return -1;
-  const gst::DevModel& h = cx->hmd[0];
-  const int ys = large_ys(cx);
-  gst::LArgs a{ds, dr, dt, cx->ls, ys, C, nsweeps, 0, record_every, mask, seed, sweep0, chain0,
+  const gst::LargePlan p = gst::plan_large(cx->hmd.data(), cx->nd, cx->debug, C, mask,
+                                           eval_only != 0, record_every > 0 && !eval_only);
+  if (!p.error.empty()) return fail(p.error);
+  if (ensure_scratch(cx, C, p.ys, p.need_g3, st)) return -1;
+  gst::LArgs a{ds, dr, dt, cx->ls, p.ys, C, nsweeps, 0, record_every, mask, seed, sweep0, chain0,
                eval_only, ow, oh};
-  const int nsb = (h.mp / 16 + 3) / 4;
-  const int npairs = nsb * (nsb + 1) / 2;
-  // kernel classes present among the batch's datasets (gst_large.hpp white_class /
-  // toa_class / hyper_class): one launch per class, each chain runs in its own dataset's
-  // class, so its arithmetic never depends on the other datasets of the batch.  Hyper blocks
-  // of up to HR_COLS (62) / HR_COLS_WIDE (126) columns: one wave per chain, register-resident
-  // elimination (lg_hyper_reg<8> / <16>); larger ones: lg_hyper (LDS)
-  const int hyper_lds = (cx->debug & GST_DEBUG_LARGE_HYPER) ? 1 : 0;
-  bool wcls[3] = {false, false, false}, tcls[2] = {false, false};
-  bool hcls[7] = {false, false, false, false, false, false, false};
-  for (const gst::DevModel& hm : cx->hmd) {
-    wcls[gst::white_class(hm.npad)] = true;
-    tcls[gst::toa_class(hm.npad)] = true;
-    const int hc = gst::hyper_class_of(hm, hyper_lds);
-    const int emt = gst::ec_reg_mt_of(hm, hyper_lds, cx->debug);
-    hcls[hc == 8 ? 0 : (hc == 16 ? 1 : (hc == 0 ? 2 : (hc == 1 ? 3 : (emt > 0 ? 4 + emt : 4))))] = true;
-  }
-  a.hyper_lds = hyper_lds;
-  const dim3 g_hr8((C + gst::HR<8>::WPB - 1) / gst::HR<8>::WPB), b_hr8(64 * gst::HR<8>::WPB);
-  const dim3 g_hr16((C + gst::HR<16>::WPB - 1) / gst::HR<16>::WPB), b_hr16(64 * gst::HR<16>::WPB);
-  // Grams of at most GS_NTMAX 16-column tiles: one wave per chain (lg_gram_small<NT>)
-  int gram_small = h.mp / 16;
-  for (const gst::DevModel& hm : cx->hmd)
-    if (hm.mp != h.mp) gram_small = 0;
-  if (gram_small > gst::GS_NTMAX || (cx->debug & GST_DEBUG_LARGE_GRAM)) gram_small = 0;
-  // datasets on the structured ECORR Gram (one tile count per batch: same structure)
-  int gram_ec_nt = 0;
-  bool gram_dense = false;
-  // lg_tmelim and lg_btm return at once for class-2 chains (the epochs-first kernels factor the
-  // timing model and draw all of b): a batch of class-2 datasets does not launch them
-  bool tm_needed = false;
-  for (const gst::DevModel& hm : cx->hmd) tm_needed = tm_needed || gst::hyper_class_of(hm, hyper_lds) != 2;
-  for (const gst::DevModel& hm : cx->hmd) {
-    if (gst::gram_ec_of(hm, hyper_lds, cx->debug))
-      gram_ec_nt = hm.gx_nt;
-    else
-      gram_dense = true;
-  }
-  const dim3 g_gs((C + gst::GS_WPB - 1) / gst::GS_WPB), b_gs(64 * gst::GS_WPB);
-  const dim3 g_gec((C + gst::GEC_CPB - 1) / gst::GEC_CPB);
-  const dim3 g_chain(C), b_chain(gst::LBLK);
-  const dim3 g_gram(npairs * ((C + gst::GRAM_WAVES - 1) / gst::GRAM_WAVES)), b_gram(64 * gst::GRAM_WAVES);
-  const dim3 g_tb(ys / 64, (C + 64 * gst::TB_CG - 1) / (64 * gst::TB_CG));
+  a.hyper_lds = p.hyper_lds;
   cx->evused = 0;
   HIP_OK(hipEventRecord(cx->ev0, st));
-  LG_LAUNCH(GST_K_TB, gst::lg_tb, g_tb, b_chain, 0);   // y = r - T b for the current b
-  const bool rec_on = record_every > 0 && !eval_only;
+  for (const gst::Launch& l : p.prologue)
+    if (run_launch(cx, p, l, a, st)) return -1;
   const int nit = eval_only ? 1 : nsweeps;
   for (int it = 0; it < nit; ++it) {
     a.it = it;
-    if (rec_on && it % record_every == 0) LG_LAUNCH(GST_K_RECORD, gst::lg_record, g_chain, b_chain, 0);
-    if (wcls[0]) {
-      a.kclass = 0;
-      LG_LAUNCH(GST_K_WHITE, gst::lg_white<gst::TBLK_WAVE>, g_chain, dim3(gst::TBLK_WAVE), 0);
-    }
-    if (wcls[1]) {
-      a.kclass = 1;
-      LG_LAUNCH(GST_K_WHITE, gst::lg_white<gst::TBLK_SMALL>, g_chain, dim3(gst::TBLK_SMALL), 0);
-    }
-    if (wcls[2]) {
-      a.kclass = 2;
-      LG_LAUNCH(GST_K_WHITE, gst::lg_white<gst::TBLK>, g_chain, dim3(gst::TBLK), 0);
-    }
-    if ((mask & (6u | GST_STAGE_GRAM)) || eval_only) {
-      if (ev_mark(cx, GST_K_GRAM, st, true)) return -1;
-      // the structured Gram for the datasets it takes (gram_ec_of), the dense one for the
-      // rest (each skips the other's chains)
-      switch (gram_ec_nt) {
-        case 1: hipLaunchKernelGGL(gst::lg_gram_ec<1>, g_gec, b_gs, 0, st, cx->dmd, a); break;
-        case 2: hipLaunchKernelGGL(gst::lg_gram_ec<2>, g_gec, b_gs, 0, st, cx->dmd, a); break;
-        case 3: hipLaunchKernelGGL(gst::lg_gram_ec<3>, g_gec, b_gs, 0, st, cx->dmd, a); break;
-        case 4: hipLaunchKernelGGL(gst::lg_gram_ec<4>, g_gec, b_gs, 0, st, cx->dmd, a); break;
-        default: break;
-      }
-      if (gram_dense) switch (gram_small) {
-        case 1: hipLaunchKernelGGL(gst::lg_gram_small<1>, g_gs, b_gs, 0, st, cx->dmd, a); break;
-        case 2: hipLaunchKernelGGL(gst::lg_gram_small<2>, g_gs, b_gs, 0, st, cx->dmd, a); break;
-        case 3: hipLaunchKernelGGL(gst::lg_gram_small<3>, g_gs, b_gs, 0, st, cx->dmd, a); break;
-        case 4: hipLaunchKernelGGL(gst::lg_gram_small<4>, g_gs, b_gs, 0, st, cx->dmd, a); break;
-        case 5: hipLaunchKernelGGL(gst::lg_gram_small<5>, g_gs, b_gs, 0, st, cx->dmd, a); break;
-        case 6: hipLaunchKernelGGL(gst::lg_gram_small<6>, g_gs, b_gs, 0, st, cx->dmd, a); break;
-        default:
-          hipLaunchKernelGGL(gst::lg_gram, g_gram, b_gram, gst::GRAM_LDS * 8, st, cx->dmd, a, nsb,
-                             npairs);
-      }
-      HIP_OK(hipGetLastError());
-      if (ev_mark(cx, GST_K_GRAM, st, false)) return -1;
-      if (!eval_only) cx->gram_large += (unsigned long long)C;
-      if (tm_needed) LG_LAUNCH(GST_K_TMELIM, gst::lg_tmelim, g_chain, b_chain, cx->lds_tm);
-      if (!(mask & GST_STAGE_GRAM)) {   // timing diagnostic: Gram + TM elimination only
-        if (launch_hyper(cx, a, hcls, g_hr8, b_hr8, g_hr16, b_hr16, g_chain, b_chain, st))
-          return -1;
-        if (eval_only) break;
-        if ((mask & 4u) && !(cx->debug & GST_DEBUG_EXACT_BDRAW)) {
-          // the b draw's floor pass (include/gst.h gst_sweep): chains whose Sigma is beyond
-          // fp64 resolution re-eliminate G with Sigma + f I and draw there; every other chain
-          // returns at once (SC_FLOOR == 0)
-          a.floor_pass = 1;
-          if (tm_needed) LG_LAUNCH(GST_K_TMELIM, gst::lg_tmelim, g_chain, b_chain, cx->lds_tm);
-          if (launch_hyper(cx, a, hcls, g_hr8, b_hr8, g_hr16, b_hr16, g_chain, b_chain, st))
-            return -1;
-          a.floor_pass = 0;
-        }
-        if (mask & 4u) {
-          if (tm_needed) LG_LAUNCH(GST_K_BTM, gst::lg_btm, g_chain, b_chain, cx->lds_btm);
-          LG_LAUNCH(GST_K_TB, gst::lg_tb, g_tb, b_chain, 0);
-        }
-      }
-    }
-    if (!eval_only && (mask & 0x78u)) {
-      if (tcls[0]) {
-        a.kclass = 0;
-        LG_LAUNCH(GST_K_TOA, gst::lg_toa<gst::TBLK_SMALL>, g_chain, dim3(gst::TBLK_SMALL), 0);
-      }
-      if (tcls[1]) {
-        a.kclass = 1;
-        LG_LAUNCH(GST_K_TOA, gst::lg_toa<gst::TBLK>, g_chain, dim3(gst::TBLK), 0);
-      }
-    }
+    for (const gst::Launch& l : p.sweep)
+      if (!(l.record && it % record_every) && run_launch(cx, p, l, a, st)) return -1;
   }
   HIP_OK(hipEventRecord(cx->ev1, st));
   cx->timed = true;
@@ -1041,41 +562,23 @@ static int launch(Ctx* cx, const gst_state* s, const gst_records* r, const gst_t
   if (cx->path == GST_PATH_LARGE)
     return launch_large(cx, ds, dr, dt, C, nsweeps, sweep0, record_every, mask, seed, chain0,
                         eval_only, ow, oh, (hipStream_t)stream);
-  // chains per workgroup: the fewest (1, 2, default) that still fit one workgroup per CU
-  int wpb = cx->WPB;
-  if (!tape) {
-    if (wpb >= 1 && C <= cx->ncu) wpb = 1;
-    else if (wpb >= 2 && C <= 2 * cx->ncu) wpb = 2;
-  }
-  // two waves per chain when every chain would otherwise leave a SIMD idle (the general
-  // white-noise instances too, since round 6)
-  const bool pair = !tape && !eval_only && !(mask & GST_STAGE_GRAM) &&
-                    (cx->waves == GST_WAVES_TWO || (cx->waves == GST_WAVES_AUTO && C <= 2 * cx->ncu));
-  kfn_t k = pick(cx->MT, cx->NS, cx->K0, cx->raug, cx->gen, tape, wpb,
-                 C > 4 * cx->ncu && cx->NS <= gst::OCC2_NS_MAX, pair);
+  const gst::PersistPlan p = gst::plan_persistent(cx->ncu, C, tape, eval_only != 0, mask, cx->waves,
+                                                  cx->NS, cx->MT, cx->K0);
+  kfn_t k = pick(cx->MT, cx->NS, cx->K0, cx->raug, cx->gen, tape, p.wpb, p.occ2, p.pair);
   if (!k) return fail("gst: no kernel instance");
-  // timing-model factor scratch: [C][waves per chain][slots with s < K0][64] doubles
-  const int ntms = cx->MT * (cx->MT + 1) / 2 - (cx->MT - cx->K0) * (cx->MT - cx->K0 + 1) / 2;
-  const size_t need = (size_t)C * (pair ? 2 : 1) * ntms * 64 * sizeof(double);
   hipStream_t st = (hipStream_t)stream;
-  if (need > cx->tmfac_bytes) {
+  if (p.tmfac_bytes > cx->tmfac_bytes) {
     free_tmfac(cx, st);
-    HIP_OK(hipMallocAsync((void**)&cx->tmfac, need, st));
-    cx->tmfac_bytes = need;
+    HIP_OK(hipMallocAsync((void**)&cx->tmfac, p.tmfac_bytes, st));
+    cx->tmfac_bytes = p.tmfac_bytes;
   }
   ds.tmfac = cx->tmfac;
-  const dim3 grid(pair ? C : (C + wpb - 1) / wpb), block(pair ? 128 : 64 * wpb);
-  // two chains per SIMD: the progress rule of fair_prio (with more chains than resident
-  // slots, the later workgroups count as behind and the launch's tail shortens: config 4
-  // 8.24 -> 8.32 M chain-sweeps/s).  Only in launches that run the red-noise block: the
-  // counter's same-address atomics serialise at ~12 ns each across the XCDs, which a full
-  // sweep hides but a stage-masked launch of a few microseconds per sweep would be timing
-  if (!tape && !pair && C > 4 * cx->ncu && (mask & GST_STAGE_HYPER)) {
+  if (p.use_prog) {
     HIP_OK(hipMemsetAsync(cx->prog, 0, sizeof(unsigned long long), st));
     ds.prog = cx->prog;
   }
   HIP_OK(hipEventRecord(cx->ev0, st));
-  hipLaunchKernelGGL(k, grid, block, 0, st, cx->dmd, ds, dr, dt, C, nsweeps, sweep0,
+  hipLaunchKernelGGL(k, dim3(p.grid), dim3(p.block), 0, st, cx->dmd, ds, dr, dt, C, nsweeps, sweep0,
                      record_every, mask, seed, chain0, eval_only, ow, oh);
   HIP_OK(hipGetLastError());
   HIP_OK(hipEventRecord(cx->ev1, st));

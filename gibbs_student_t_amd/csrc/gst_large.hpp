@@ -27,100 +27,11 @@
 #include <hip/hip_runtime.h>
 
 #include "gst_kernel.hpp"
+#include "gst_plan.h"
 
 namespace gst {
 
-constexpr int LBLK = 256;      // threads of the per-chain kernels (4 waves)
 constexpr double LN10 = 2.302585092994045684;
-// threads per chain of the per-TOA passes (lg_white, lg_toa): 16 waves per chain for the
-// 100k-TOA datasets; 4 for datasets of up to TBLK_SMALL_NPAD TOAs, where a pass is a few
-// TOAs per thread and a 16-wave chain spent it in barriers and reductions with one chain per
-// CU.  The block size sets the reduction order, so it is chosen PER DATASET (kernel classes
-// below), never from the launch's other datasets or its chain count: a dataset's chains are
-// the same launched alone, batched with any others, or split over launches and ranks.
-constexpr int TBLK = 1024;
-constexpr int TBLK_SMALL = 256;
-constexpr int TBLK_SMALL_NPAD = 32768;
-// lg_white only: one wave per chain up to 8k TOAs (its 21 likelihood passes are then a few
-// loads and one wave reduction each, with no workgroup barrier)
-constexpr int TBLK_WAVE = 64;
-constexpr int TBLK_WAVE_NPAD = 8192;
-// Kernel classes of a dataset (the host launches one kernel per class present in a batch;
-// a chain whose dataset is of another class returns at once):
-//   lg_white: 0 = one wave (npad <= TBLK_WAVE_NPAD), 1 = TBLK_SMALL, 2 = TBLK threads;
-//   lg_toa:   0 = TBLK_SMALL, 1 = TBLK threads;
-//   hyper:    8 / 16 = lg_hyper_reg<8 / 16> (hyper block of <= 62 / 126 columns), 0 = lg_hyper
-//             (LDS-resident block, <= HYPER_LDS_MAX columns), 1 = lg_hyper<1> (larger blocks:
-//             blocked elimination in global memory), 2 = lg_hyper<2> (larger blocks made of
-//             ECORR epochs -- hundreds of them -- around a small timing-model + Fourier block:
-//             the epochs eliminated first, see lg_hyper).
-__host__ __device__ constexpr int white_class(int npad) {
-  return npad <= TBLK_WAVE_NPAD ? 0 : (npad <= TBLK_SMALL_NPAD ? 1 : 2);
-}
-__host__ __device__ constexpr int toa_class(int npad) { return npad <= TBLK_SMALL_NPAD ? 0 : 1; }
-// hyper class from the dataset's own hyper block nf + nec: lg_hyper_reg<MT> takes up to
-// HR<MT>::RA = 8 MT - 2 columns (62 / 126)
-constexpr int HYPER_LDS_MAX = 138;   // lg_hyper's LDS block: (ms (ms + 1) + 3 ms) doubles < 160 KB
-// lg_hyper<2>: the timing-model + Fourier + augmented-row block X it factors per likelihood
-// (qx = ntm + nfourier + 1 rows) is at most EC_QX_MAX (its lower 16x16 tiles, at most
-// EC_TPW per wave, accumulate in MFMA registers); the epochs' couplings stream through LDS
-// EC_ECH epochs at a time
-constexpr int EC_QX_MAX = 76;
-constexpr int EC_TPW = 4;
-constexpr int EC_ECH = 32;
-static_assert(((EC_QX_MAX + 15) / 16) * ((EC_QX_MAX + 15) / 16 + 1) / 2 <= EC_TPW * (LBLK / 64),
-              "lg_hyper<2> tiles per wave");
-// (force_lds: GST_DEBUG_LARGE_HYPER, the generic kernels: class 0, or 1 past HYPER_LDS_MAX)
-// Class 2 (epochs first) for every block past HYPER_LDS_MAX it can take, and for blocks past
-// lg_hyper_reg<8>'s 62 columns whose ECORR epochs outnumber X's rows (measured: mb, 20
-// Fourier + 60 epochs, 1.8-2.1x over lg_hyper_reg<16>; ecb, 20 + 24, 0.54-0.85x of
-// lg_hyper_reg<8>)
-// Class 2 needs disjoint epochs (each TOA in at most one ECORR column: the ECORR block of
-// T^T N^-1 T is then diagonal, which its elimination assumes); gst_model_set checks the basis
-// (DevModel::ec_disjoint) and other ECORR bases take class 1 / the register kernels.
-__host__ __device__ constexpr int hyper_class(int hcols, int force_lds, int nec, int qx,
-                                              int disjoint = 1) {
-  return (nec > 0 && disjoint && qx <= EC_QX_MAX && !force_lds &&
-          (hcols > HYPER_LDS_MAX || (hcols > 8 * 8 - 2 && nec >= qx)))
-             ? 2
-         : hcols > HYPER_LDS_MAX ? 1
-                                 : (force_lds ? 0 : (hcols <= 8 * 8 - 2 ? 8 : (hcols <= 8 * 16 - 2 ? 16 : 0)));
-}
-__host__ __device__ inline int hyper_class_of(const DevModel& md, int force_lds) {
-  return hyper_class(md.nf + md.nec, force_lds, md.nec, md.ntm + md.nf + 1, md.ec_disjoint);
-}
-// Epochs-first chains (class 2) whose timing model has <= 16 columns and whose Fourier block
-// fits the register layout run lg_hyper_ecr<MT, RA> (one wave per chain, MT = 6 / 8: Fourier
-// blocks of <= 30 / 46 columns) instead of lg_hyper<2>; 0: lg_hyper<2> (also under
-// GST_DEBUG_EPOCHS_LDS or GST_DEBUG_LARGE_HYPER)
-// (instance id: 1 = <6, 46>, 2 = <8, 62>: (MT, augmented row); an instance <6, 38> for
-// Fourier blocks of <= 22 columns, cutting eight pad steps, spilled 148 B/lane and measured
-// no faster on ebig / mb)
-// (and at most EC_REG_MAX epochs: their pivots and augmented-row entries live in registers)
-constexpr int EC_REG_MAX = 192;
-__host__ __device__ constexpr int ec_reg_mt(int hclass, int ntm, int nf, int nec, int debug) {
-  return (hclass != 2 || ntm > 16 || nec > EC_REG_MAX || (debug & DEBUG_EPOCHS_LDS)) ? 0
-         : (16 + nf <= 46 ? 1 : (16 + nf <= 62 ? 2 : 0));
-}
-__host__ __device__ inline int ec_reg_mt_of(const DevModel& md, int force_lds, int debug) {
-  return ec_reg_mt(hyper_class_of(md, force_lds), md.ntm, md.nf, md.nec, debug);
-}
-// Chains whose dataset has disjoint ECORR epochs and runs them epochs first (class 2) take the
-// structured Gram lg_gram_ec (DevModel::gx_nt > 0), which computes only the blocks class 2 reads:
-// G_xx (X = timing model, Fourier, r), the epochs' diagonal and their couplings to X.  The
-// dense Grams (lg_gram, lg_gram_small) skip these chains.  GST_DEBUG_LARGE_GRAM: dense.
-__host__ __device__ inline bool gram_ec_of(const DevModel& md, int force_lds, int debug) {
-  return md.gx_nt > 0 && !(debug & DEBUG_LARGE_GRAM) && hyper_class_of(md, force_lds) == 2;
-}
-constexpr int GRAM_WAVES = 8;  // chains per gram workgroup
-#ifndef GST_TM_PW
-#define GST_TM_PW 16   // A/B builds override it (32: config-5 tmelim 1.75 -> 2.95 ms, ebig -20%)
-#endif
-constexpr int TM_PW = GST_TM_PW;   // panel width of the blocked eliminations (panel_ldl)
-#ifndef GST_TM_TILES
-#define GST_TM_TILES 4   // (8: measured no faster on config 5, round 6)
-#endif
-constexpr int TM_TILES = GST_TM_TILES;   // trailing-update tiles per wave per round (panel_ldl)
 
 struct LScratch {
   double* G;   // [C][mp*mp] Gram (row-major, lower triangle); kept for the floor pass
@@ -687,8 +598,6 @@ __global__ void __launch_bounds__(TB) lg_white(const DevModel* __restrict__ mds,
 // double-buffered: chunk i+1 is fetched into registers while chunk i feeds the MFMAs, so
 // every T element is read from L2/HBM once per workgroup and the MFMAs never wait on a
 // global load.  Each wave scales its A operand by its own chain's weights (LDS too).
-constexpr int GRAM_KC = 16;                       // k-steps (of 4 TOAs) per chunk
-constexpr int GRAM_LDS = 2 * GRAM_KC * 8 * 64 + 2 * GRAM_WAVES * 64;   // doubles
 
 // Inner loop + store of one super-tile; the valid tile pattern (NU rows of tiles, diagonal
 // or not) is a template parameter, so the 16 MFMAs of a k-step are straight-line code (with
@@ -858,8 +767,6 @@ __global__ void __launch_bounds__(64 * GRAM_WAVES) lg_gram(const DevModel* __res
 // 10 / 4 / 1 tiles), and the diagonal one set the time.  Every tile receives the same MFMA
 // sequence as in lg_gram (k-steps in order, A = T w, B = T), so G is bitwise lg_gram's.
 // ------------------------------------------------------------------------------------
-constexpr int GS_NTMAX = 6;
-constexpr int GS_WPB = 4;
 constexpr int GS_DEPTH = 4;
 template <int NT>
 __global__ void __launch_bounds__(64 * GS_WPB) lg_gram_small(const DevModel* __restrict__ mds,
@@ -940,7 +847,6 @@ __global__ void __launch_bounds__(64 * GS_WPB) lg_gram_small(const DevModel* __r
 // blocks are exactly zero and never read).  Two waves per chain: G_xx and the epochs' blocks
 // (their MFMAs share the SIMD's pipe; the second wave hides the first's load latency).
 // ------------------------------------------------------------------------------------
-constexpr int GEC_CPB = GS_WPB / 2;   // chains per lg_gram_ec workgroup
 template <int NX>
 __global__ void __launch_bounds__(64 * GS_WPB) lg_gram_ec(const DevModel* __restrict__ mds,
                                                             LArgs a) {
@@ -1201,7 +1107,7 @@ __global__ void __launch_bounds__(LBLK) lg_tmelim(const DevModel* __restrict__ m
   if (a.floor_pass && !(fsh > 0.0)) return;
   if (hyper_class_of(md, a.hyper_lds) == 2) return;   // lg_hyper<2> factors the timing model
   extern __shared__ double lsm[];
-  double* P = lsm;                     // [mp][TM_PW + 1]
+  double* P = lsm;                     // TmelimLds: [mp][TM_PW + 1]
   __shared__ double ainv[TM_PW];
   const int mp = md.mp, K0 = md.ntm_pad;
   // G stays the Gram (the floor pass re-eliminates it); the factor and S0 go to G2
@@ -1486,7 +1392,10 @@ __global__ void __launch_bounds__(LBLK) lg_hyper(const DevModel* __restrict__ md
   // EC: X's rows: ntm timing-model columns, nfr Fourier columns, the augmented row (nxd = qx-1)
   const int qx = ntm + nfr + 1, nxd = qx - 1, qxp = (qx + 15) & ~15;
   const int SS = BIG ? mp : (EC ? qx + 1 : ms + 1);
-  // LDS: S [ms][SS] (BIG: the panel [mp][TM_PW + 1] and 1 / a_kk [TM_PW] instead; EC: X
+  // LDS, carved by hand in the order of HyperLds<MODE> (gst_plan.h), which is the host's only
+  // source for the size: a region added or resized here must change there too.  (Carved from
+  // the layout's offsets lg_hyper<1> compiled to other code and ran 1.0-1.7% slower.)
+  // S [ms][SS] (BIG: the panel [mp][TM_PW + 1] and 1 / a_kk [TM_PW] instead; EC: X
   // [qx][SS] and its epochs-eliminated base XB [qx][SS], then the vectors below sized mp, the
   // pivots a_e, one chunk of couplings [EC_ECH][qxp])
   double* P = lsm;
@@ -1999,7 +1908,7 @@ template <int MT>
 struct HR {
   static constexpr int RA = 8 * MT - 2;        // augmented row (the paired tail covers an
                                                // even number of columns from slot KP)
-  static constexpr int WPB = MT <= 8 ? 4 : 2;  // chains (waves) per workgroup
+  static constexpr int WPB = hr_wpb(MT);       // chains (waves) per workgroup
   static constexpr int KP = MT <= 8 ? kp_for(1) : MT;
   static constexpr int NCS = (8 * MT + 63) / 64;   // hyper columns per lane (64 sl + lane)
   static constexpr int S0 = 64 * SL(MT, 0);        // S0 [slot][lane]
@@ -2188,7 +2097,7 @@ struct HE {
   static constexpr int RA = RA_;                 // augmented row (<= 8 MT - 2)
   static constexpr int ID = MT == 8 ? 2 : 1;     // ec_reg_mt's instance id
   static constexpr int KT = 2;                   // timing-model slot columns (ntm <= 16)
-  static constexpr int WPB = MT <= 6 ? 4 : 2;    // chains (waves) per workgroup (he_wpb)
+  static constexpr int WPB = he_wpb(MT);         // chains (waves) per workgroup
   static constexpr int KP = kp_for(1);
   static constexpr int NSL = SL(MT, 0);
   static constexpr int EG = 4;                   // epochs per staged group
@@ -2203,7 +2112,6 @@ struct HE {
                              4 * NHYPER + 64 + 64 + 2 * PMAX + NBMAX + 3 * 64 * EC_NEB;
 };
 
-__host__ __device__ constexpr int he_wpb(int MT) { return MT <= 6 ? 4 : 2; }
 template <int MT, int RA_>
 __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevModel* __restrict__ mds,
                                                                       LArgs a) {
@@ -2529,10 +2437,11 @@ __global__ void __launch_bounds__(LBLK) lg_btm(const DevModel* __restrict__ mds,
   const DevModel& md = mds[ds_of(a, c)];
   extern __shared__ double lsm[];
   const int K0 = md.ntm_pad, mp = md.mp, raug = md.raug;
+  const BtmLds lay(K0, raug);
   double* acc = lsm;          // [K0]
-  double* wk = acc + K0;      // [K0]
-  double* vt = wk + K0;       // [K0] solution, timing-model block
-  double* dl = vt + K0;       // [raug] Delta (tape mode)
+  double* wk = lsm + lay.wk;  // [K0]
+  double* vt = lsm + lay.vt;  // [K0] solution, timing-model block
+  double* dl = lsm + lay.dl;  // [raug] Delta (tape mode)
   __shared__ double bc[2];
   const int tid = threadIdx.x;
   const double* sc = a.s.sc + (size_t)c * 16;
@@ -2592,7 +2501,6 @@ __global__ void __launch_bounds__(LBLK) lg_btm(const DevModel* __restrict__ mds,
 // groups of a wave share the B fragments (CG x 4 MFMAs per CG + 4 loads), with TB_DEPTH
 // k-steps of operands in flight.  Every y element receives the same MFMA sequence (k in
 // order, the same A / B values) whatever CG is, so y is bitwise that of one group per wave.
-constexpr int TB_CG = 4;      // 16-chain groups per wave (chains per wave: 64)
 #ifndef GST_TB_DEPTH
 #define GST_TB_DEPTH 2   // (3: measured no faster on config 5, round 6)
 #endif

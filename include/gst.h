@@ -304,9 +304,12 @@ int gst_last_sweep_ms(void* ctx, double* ms);
  *              update per flagged TOA, on the VALU (<= 8 noise classes, <= 32 flagged TOAs,
  *              every flagged alpha <= 2^20);
  *   counts[1]  persistent kernel, the n-TOA fp64 MFMA Gram;
- *   counts[2]  large path, fp64 MFMA Gram (lg_gram / lg_gram_small), chains x launches.
- * One count per chain per Gram (the floor pass recomputes it: counted again).  Synchronises
- * the device.  reset != 0 zeroes the counters after reading them. */
+ *   counts[2]  large path: the launch's chain count per Gram stage of a sweep, whichever
+ *              kernels ran it (lg_gram, lg_gram_small, lg_gram_ec), chains that a kernel
+ *              skipped included.  The b draw's floor pass re-eliminates the same Gram: it is
+ *              not computed, and not counted, again.
+ * counts[0] and counts[1]: one count per chain per Gram computed.  Synchronises the device.
+ * reset != 0 zeroes the counters after reading them. */
 int gst_gram_counts(void* ctx, long long* counts, int reset);
 
 /* Test hook (ABI 6): n draws of the kernel's own samplers into the DEVICE array out, Philox

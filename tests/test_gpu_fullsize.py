@@ -72,3 +72,38 @@ def test_fullsize_sampler_and_likelihoods(big):
             else:
                 assert h[c] == h_ref
     g.close()
+
+
+def test_largest_lds_hyper_block():
+    """69 Fourier components: the 138-column hyper block is the largest that lg_hyper<0>
+    factors in LDS (HYPER_LDS_MAX, its layout of 155 KiB).  Both likelihoods of 64 chains
+    against the oracle at states the sampler reached, at this file's tolerance."""
+    psr = data.scaled_synthetic(n=512, components=69, ntm=3, seed=8)
+    pta = PTA(psr, components=69)
+    assert pta.T.shape == (512, 138 + 3)
+    C = 64
+    g = Gibbs(pta, **KW, nchains=C, seed=23)
+    assert g._native.path == "large"
+    rng = np.random.default_rng(4)
+    lo = np.array([p.pmin for p in pta.params])
+    hi = np.array([p.pmax for p in pta.params])
+    x = g.sample(rng.uniform(lo, hi, size=(C, len(lo))), niter=2)
+    assert np.all((g.status & STATUS_ERRORS) == 0)
+    w, h = g.get_lnlikelihood_white(x), g.get_lnlikelihood(x)
+    orc = Oracle(pta, OutlierModel(**KW))
+    for c in range(C):
+        st = ChainState(b=g._b_all[c].copy(), z=g._z_all[c].copy(), alpha=g._alpha_all[c].copy(),
+                        pout=g._pout_all[c].copy(), theta=float(g._theta_all[c]),
+                        nu=float(g._tdf_all[c]))
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            w_ref = orc.lnlike_white(st, x[c])
+            orc.cache = None
+            h_ref = orc.lnlike_marginal(st, x[c])
+        assert abs(w[c] - w_ref) <= 1e-10 * abs(w_ref), (c, w[c], w_ref)
+        if np.isfinite(h_ref):
+            assert abs(h[c] - h_ref) <= 1e-10 * abs(h_ref), (c, h[c], h_ref)
+        else:
+            assert h[c] == h_ref
+    assert np.sum(np.isfinite(h)) > C // 2
+    g.close()
