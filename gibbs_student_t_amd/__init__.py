@@ -14,6 +14,6 @@ def __getattr__(name):
     import importlib
     if name == "Gibbs":
         return importlib.import_module(__name__ + ".sampler").Gibbs
-    if name in ("data", "build", "native", "sampler", "diag", "dist"):
+    if name in ("data", "build", "native", "sampler", "diag", "dist", "post"):
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

@@ -36,19 +36,21 @@ def floor_draws(status):
     import numpy as np
     return np.asarray(status) >> STATUS_FLOOR_COUNT_SHIFT
 PATHS = {"auto": PATH_AUTO, "persistent": PATH_PERSISTENT, "large": PATH_LARGE}
-KERNEL_KINDS = ("record", "white", "gram", "tmelim", "hyper", "btm", "tb", "toa")
+KERNEL_KINDS = ("record", "white", "gram", "tmelim", "hyper", "btm", "tb", "toa", "accum")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 EXPORTS = ("gst_version", "gst_tape_stride", "gst_last_error", "gst_ctx_create",
            "gst_ctx_destroy", "gst_model_set", "gst_model_set_batch", "gst_model_info",
            "gst_sweep", "gst_set_path", "gst_get_path", "gst_set_waves", "gst_set_debug", "gst_set_timing", "gst_kernel_times", "gst_eval_lnlike", "gst_sync",
            "gst_last_sweep_ms", "gst_debug_stamps", "gst_simulate",
            # ABI 6
-           "gst_gram_counts", "gst_debug_variates")
+           "gst_gram_counts", "gst_debug_variates",
+           # ABI 7
+           "gst_set_accum")
 
-# diagnostics that older builds (A/B timing of library variants) may lack; calling one on
+# entry points that older builds (A/B timing of library variants) may lack; calling one on
 # such a build raises AttributeError
-OPTIONAL = ("gst_set_debug", "gst_gram_counts", "gst_debug_variates")
+OPTIONAL = ("gst_set_debug", "gst_gram_counts", "gst_debug_variates", "gst_set_accum")
 
 _P = ct.POINTER
 _D = _P(ct.c_double)
@@ -89,6 +91,13 @@ class Records(ct.Structure):
     _fields_ = [("x", ct.c_void_p), ("b", ct.c_void_p), ("z", ct.c_void_p),
                 ("alpha", ct.c_void_p), ("pout", ct.c_void_p), ("theta", ct.c_void_p),
                 ("nu", ct.c_void_p), ("nrec", ct.c_int)]
+
+
+class Accum(ct.Structure):
+    """gst_accum: posterior sums on the device (device pointers, any may be None)."""
+    _fields_ = [("z_sum", ct.c_void_p), ("pout_sum", ct.c_void_p), ("alpha_sum", ct.c_void_p),
+                ("b_sum", ct.c_void_p), ("b_sq", ct.c_void_p), ("count", ct.c_void_p),
+                ("from_sweep", ct.c_longlong)]
 
 
 class Tape(ct.Structure):
@@ -148,6 +157,8 @@ def load(path: str | None = None):
     lib.gst_eval_lnlike.argtypes = [ct.c_void_p, _P(State), ct.c_int, ct.c_void_p,
                                     ct.c_void_p, ct.c_void_p]
     lib.gst_sync.argtypes = [ct.c_void_p, ct.c_void_p]
+    if hasattr(lib, "gst_set_accum"):
+        lib.gst_set_accum.argtypes = [ct.c_void_p, _P(Accum)]
     lib.gst_set_path.argtypes = [ct.c_void_p, ct.c_int]
     lib.gst_get_path.argtypes = [ct.c_void_p, _P(ct.c_int)]
     lib.gst_set_waves.argtypes = [ct.c_void_p, ct.c_int]

@@ -54,6 +54,11 @@ struct Ctx {
   int debug = 0;                   // gst_set_debug
   unsigned long long* gram_cnt = nullptr;  // persistent path: [2] Grams by path (gst_gram_counts)
   unsigned long long gram_large = 0;       // large path: chain Grams launched (lg_gram*)
+  // posterior sums (gst_set_accum): the caller's descriptor and whether its device copy
+  // (behind gram_cnt's two counters, gst::accum_desc) is behind: the next accumulating launch
+  // rewrites it in stream order
+  gst_accum acc{};
+  bool acc_on = false, acc_dirty = false;
   std::vector<void*> allocs;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -114,12 +119,13 @@ using gst::kfn_t;
 // occ2: the two-chains-per-SIMD build (256 registers per lane), picked when the launch has
 // more chains than SIMDs; with at most one chain per SIMD the uncapped build keeps more of
 // each chain in registers.  pair: two waves per chain (gst_set_waves).
-// gen: the general white-noise model's instances (GEN shapes).
+// gen: the general white-noise model's instances (GEN shapes).  acc: the instance that keeps
+// the posterior sums (gst_set_accum).
 kfn_t pick(int MT, int NS, int K0, int RA, bool gen, bool tape, int wpb, bool occ2,
-           bool pair = false) {
+           bool pair = false, bool acc = false) {
 #define GST_CASE(mt, ns, k0, ra, g)                                              \
   if (MT == mt && NS == ns && K0 == k0 && RA == ra && (gen ? 1 : 0) == g)        \
-    return gst::GST_PICK_NAME(mt, ns, k0, ra, g)(tape, wpb, occ2, pair);
+    return gst::GST_PICK_NAME(mt, ns, k0, ra, g)(tape, wpb, occ2, pair, acc);
   GST_SHAPES(GST_CASE)
 #undef GST_CASE
   return nullptr;
@@ -230,8 +236,9 @@ int gst_ctx_create(int device, void** ctx) {
   HIP_OK(hipEventCreate(&cx->ev0));
   HIP_OK(hipEventCreate(&cx->ev1));
   HIP_OK(hipMalloc(&cx->prog, 256));   // fair_prio's launch-wide sweep counter
-  HIP_OK(hipMalloc(&cx->gram_cnt, 2 * sizeof(unsigned long long)));
-  HIP_OK(hipMemset(cx->gram_cnt, 0, 2 * sizeof(unsigned long long)));
+  const size_t cnt_bytes = 2 * sizeof(unsigned long long) + sizeof(gst::DevAccum);
+  HIP_OK(hipMalloc(&cx->gram_cnt, cnt_bytes));
+  HIP_OK(hipMemset(cx->gram_cnt, 0, cnt_bytes));
   *ctx = cx;
   return 0;
 }
@@ -490,7 +497,7 @@ static const lkfn_t kLargeKernels[gst::LK_COUNT] = {
     gst::lg_hyper_reg<8>, gst::lg_hyper_reg<16>, gst::lg_hyper<0>, gst::lg_hyper<1>,
     gst::lg_hyper<2>, gst::lg_hyper_ecr<6, 46>, gst::lg_hyper_ecr<8, 62>,
     gst::lg_btm,
-    gst::lg_toa<gst::TBLK_SMALL>, gst::lg_toa<gst::TBLK>};
+    gst::lg_toa<gst::TBLK_SMALL>, gst::lg_toa<gst::TBLK>, gst::lg_accum};
 
 static int run_launch(Ctx* cx, const gst::LargePlan& p, const gst::Launch& l, gst::LArgs& a,
                       hipStream_t st) {
@@ -514,10 +521,11 @@ static int run_launch(Ctx* cx, const gst::LargePlan& p, const gst::Launch& l, gs
 static int launch_large(Ctx* cx, const gst::DevState& ds, const gst::DevRec& dr,
                         const gst::DevTape& dt, int C, int nsweeps, long long sweep0,
                         int record_every, unsigned mask, unsigned long long seed,
-                        long long chain0, int eval_only, double* ow, double* oh,
+                        long long chain0, int eval_only, bool acc_on, double* ow, double* oh,
                         hipStream_t st) {
   const gst::LargePlan p = gst::plan_large(cx->hmd.data(), cx->nd, cx->debug, C, mask,
-                                           eval_only != 0, record_every > 0 && !eval_only);
+                                           eval_only != 0, record_every > 0 && !eval_only,
+                                           acc_on);
   if (!p.error.empty()) return fail(p.error);
   if (ensure_scratch(cx, C, p.ys, p.need_g3, st)) return -1;
   gst::LArgs a{ds, dr, dt, cx->ls, p.ys, C, nsweeps, 0, record_every, mask, seed, sweep0, chain0,
@@ -530,13 +538,20 @@ static int launch_large(Ctx* cx, const gst::DevState& ds, const gst::DevRec& dr,
   const int nit = eval_only ? 1 : nsweeps;
   for (int it = 0; it < nit; ++it) {
     a.it = it;
-    for (const gst::Launch& l : p.sweep)
-      if (!(l.record && it % record_every) && run_launch(cx, p, l, a, st)) return -1;
+    for (const gst::Launch& l : p.sweep) {
+      if (l.record && it % record_every) continue;
+      if (l.kernel == gst::LK_ACCUM && sweep0 + it < cx->acc.from_sweep) continue;
+      if (run_launch(cx, p, l, a, st)) return -1;
+    }
   }
   HIP_OK(hipEventRecord(cx->ev1, st));
   cx->timed = true;
   return 0;
 }
+
+// The context's device copy of the accumulator descriptor is written by a kernel, so that it
+// is ordered on the stream with the launches that read it
+static __global__ void set_accum_kernel(gst::DevAccum* dst, gst::DevAccum v) { *dst = v; }
 
 static int launch(Ctx* cx, const gst_state* s, const gst_records* r, const gst_tape* tp,
                   int C, int nsweeps, long long sweep0, int record_every, unsigned mask,
@@ -553,6 +568,18 @@ static int launch(Ctx* cx, const gst_state* s, const gst_records* r, const gst_t
   gst::DevState ds{s->x,     s->b,  s->z,      s->alpha,   s->pout, s->theta,
                    s->nu,    s->status, s->dataset, cx->nmax, cx->nd, nullptr, nullptr,
                    cx->debug, eval_only ? nullptr : cx->gram_cnt};
+  // posterior sums: sampling launches that reach from_sweep (never eval_only / GST_STAGE_GRAM)
+  const bool acc_on = cx->acc_on && !eval_only && !(mask & GST_STAGE_GRAM) &&
+                      sweep0 + nsweeps > cx->acc.from_sweep;
+  if (acc_on && cx->acc_dirty) {
+    const gst_accum& h = cx->acc;
+    hipLaunchKernelGGL(set_accum_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
+                       gst::accum_desc(cx->gram_cnt),
+                       gst::DevAccum{h.z_sum, h.pout_sum, h.alpha_sum, h.b_sum, h.b_sq, h.count,
+                                     h.from_sweep});
+    HIP_OK(hipGetLastError());
+    cx->acc_dirty = false;
+  }
   gst::DevRec dr{};
   if (r) dr = gst::DevRec{r->x, r->b, r->z, r->alpha, r->pout, r->theta, r->nu, r->nrec};
   else record_every = 0;
@@ -561,10 +588,11 @@ static int launch(Ctx* cx, const gst_state* s, const gst_records* r, const gst_t
   gst::DevTape dt{tape ? tp->data : nullptr, tape ? tp->stride : 0};
   if (cx->path == GST_PATH_LARGE)
     return launch_large(cx, ds, dr, dt, C, nsweeps, sweep0, record_every, mask, seed, chain0,
-                        eval_only, ow, oh, (hipStream_t)stream);
+                        eval_only, acc_on, ow, oh, (hipStream_t)stream);
   const gst::PersistPlan p = gst::plan_persistent(cx->ncu, C, tape, eval_only != 0, mask, cx->waves,
                                                   cx->NS, cx->MT, cx->K0);
-  kfn_t k = pick(cx->MT, cx->NS, cx->K0, cx->raug, cx->gen, tape, p.wpb, p.occ2, p.pair);
+  kfn_t k = pick(cx->MT, cx->NS, cx->K0, cx->raug, cx->gen, tape, p.wpb, p.occ2, p.pair,
+                 acc_on);
   if (!k) return fail("gst: no kernel instance");
   hipStream_t st = (hipStream_t)stream;
   if (p.tmfac_bytes > cx->tmfac_bytes) {
@@ -601,6 +629,15 @@ int gst_eval_lnlike(void* ctx, const gst_state* state, int nchains, double* out_
   if (!out_white || !out_hyper) return fail("gst_eval_lnlike: null outputs");
   return launch(static_cast<Ctx*>(ctx), state, nullptr, nullptr, nchains, 0, 0, 0, 0u, 0ull,
                 0, 1, out_white, out_hyper, stream);
+}
+
+int gst_set_accum(void* ctx, const gst_accum* acc) {
+  Ctx* cx = static_cast<Ctx*>(ctx);
+  if (!cx) return fail("gst_set_accum: null ctx");
+  cx->acc_on = acc != nullptr;
+  cx->acc = acc ? *acc : gst_accum{};
+  cx->acc_dirty = cx->acc_on;
+  return 0;
 }
 
 int gst_debug_stamps(void* ctx, unsigned long long* dev_buf) {

@@ -866,8 +866,13 @@ __device__ __forceinline__ void chol_stats(CholCtx& cc) {
 // (DESIGN.md section 8).
 // GEN: the general white-noise model (per-backend efac / equad, ECORR epoch columns in the
 // hyper block, up to 8 parameters; gibbs.py:64-77); pair mode too since round 6.
+// ACC: the instances that keep the posterior sums (gst_set_accum), launched only while the
+// sums are set.  Instances of their own because the sweep kernel sits at the register limit
+// (most instances spill): the same code behind a run-time test moved the allocation of the
+// whole kernel (J1713 two-chains-per-SIMD instance: scratch 340 -> 372 B/lane), while a
+// template parameter leaves every other instance's code, and so its registers, as they were.
 template <int MT, int NS, int K0, int RA, bool TAPE, int WPB = 4, int OCC = 1, bool PAIR = false,
-          bool GEN = false>
+          bool GEN = false, bool ACC = false>
 __global__ void __launch_bounds__(64 * WPB, OCC)
     gst_sweep_kernel(const DevModel* __restrict__ mds, const DevState st, const DevRec rec, const DevTape tape,
                      int C, int nsweeps, long long sweep0, int record_every, unsigned mask,
@@ -1691,6 +1696,43 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
           if (rec.theta) rec.theta[base] = theta;
           if (rec.nu) rec.nu[base] = nu;
         }
+      }
+    }
+
+    // ---- posterior sums (gst_set_accum): the same state, added into the caller's running
+    // sums on every sweep from from_sweep on.  Each element has one owner (the records' split:
+    // pair mode divides the b columns and the TOA slots by role) and is a plain read-modify-
+    // write in sweep order, so a sum is bitwise the sequential sum of the records.  The host
+    // launches an ACC instance only while sums are set (never eval_only or GST_STAGE_GRAM).
+    if constexpr (ACC) {
+      // the descriptor is read here with scalar loads each sweep, not kept in registers
+      // across the sweep: the asm keeps the loads from being hoisted out of the loop
+      const DevAccum* ap = accum_desc(st.gram_cnt);
+      asm volatile("" : "+s"(ap));
+      const __attribute__((address_space(4))) DevAccum& A =
+          *(const __attribute__((address_space(4))) DevAccum*)ap;
+      if (sweep0 + it >= A.from_sweep) {
+        if (double* const sb = A.b_sum)
+          for (int j = lane + 64 * role; j < m; j += (PAIR ? 128 : 64)) sb[(size_t)c * m + j] += brow[j];
+        if (double* const sq = A.b_sq)
+          for (int j = lane + 64 * role; j < m; j += (PAIR ? 128 : 64)) {
+            const double v = brow[j];
+            sq[(size_t)c * m + j] += v * v;
+          }
+        double* const sz = A.z_sum;
+        double* const sa = A.alpha_sum;
+        double* const sp = A.pout_sum;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const size_t e = (size_t)c * nst + 64 * s + lane;
+          if ((vmask & (1u << s)) && (!PAIR || (s & 1) == role)) {
+            if (sz) sz[e] += (double)((zb >> s) & 1u);
+            if (sa) sa[e] += al[s];
+            if (sp) sp[e] += po[s];
+          }
+        }
+        if (lane == 0 && role == 0)
+          if (long long* const cnt = A.count) cnt[c] += 1;
       }
     }
 

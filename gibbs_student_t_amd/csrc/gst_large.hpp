@@ -309,6 +309,32 @@ __global__ void __launch_bounds__(LBLK) lg_record(const DevModel* __restrict__ m
 }
 
 // ------------------------------------------------------------------------------------
+// accum: the posterior sums (gst_set_accum) of the state at the start of the sweep, the values
+// lg_record stores.  A kernel of its own: lg_record is skipped on thinned sweeps, the sums
+// count every sweep (the host skips the launch before from_sweep).  One workgroup per chain,
+// one owner per element, a plain sum = sum + v in sweep order.
+// ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(LBLK) lg_accum(const DevModel* __restrict__ mds, LArgs a) {
+  const int c = blockIdx.x;
+  if (c >= a.C) return;
+  const DevAccum A = *accum_desc(a.st.gram_cnt);
+  const DevModel& md = mds[ds_of(a, c)];
+  const int n = md.n, m = md.m, nst = a.st.nst;
+  const size_t rb = (size_t)c * m, rt = (size_t)c * nst;
+  for (int j = threadIdx.x; j < m; j += LBLK) {
+    const double v = a.st.b[rb + j];
+    if (A.b_sum) A.b_sum[rb + j] += v;
+    if (A.b_sq) A.b_sq[rb + j] += v * v;
+  }
+  for (int t = threadIdx.x; t < n; t += LBLK) {
+    if (A.z_sum) A.z_sum[rt + t] += a.st.z[rt + t];
+    if (A.alpha_sum) A.alpha_sum[rt + t] += a.st.alpha[rt + t];
+    if (A.pout_sum) A.pout_sum[rt + t] += a.st.pout[rt + t];
+  }
+  if (threadIdx.x == 0 && A.count) A.count[c] += 1;
+}
+
+// ------------------------------------------------------------------------------------
 // white: MH over the white-noise parameters, then N^-1 for the Gram
 // ------------------------------------------------------------------------------------
 template <int TB>

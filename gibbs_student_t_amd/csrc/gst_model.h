@@ -129,6 +129,16 @@ struct DevModel {
   unsigned long long* stamps;  // diagnostic build only (GST_STAMPS): [C][GST_NSTAMP]
 };
 
+// gst_accum (posterior sums, gst_set_accum): the context's device copy, which the accumulating
+// kernels (the sweep kernel's ACC instances, lg_accum) read with scalar loads.  It lies behind
+// the two Gram counters of DevState::gram_cnt (accum_desc below) and not in DevState, whose
+// layout -- the kernels' argument layout -- stays as it is: the sweep kernel sits at the
+// register limit, and one more pointer in DevState alone moved the allocation of 81 instances.
+struct DevAccum {
+  double *z_sum, *pout_sum, *alpha_sum, *b_sum, *b_sq;
+  long long* count;
+  long long from_sweep;
+};
 struct DevState {
   double *x, *b, *z, *alpha, *pout, *theta, *nu;
   int* status;
@@ -139,8 +149,12 @@ struct DevState {
   unsigned long long* prog;  // chain-sweeps started in this launch (two chains per SIMD), or
                              // null: see fair_prio
   int debug;                 // GST_DEBUG_* flags (gst_set_debug)
-  unsigned long long* gram_cnt;  // [2] Grams computed: low-rank, MFMA (gst_gram_counts), or null
+  unsigned long long* gram_cnt;  // [2] Grams computed: low-rank, MFMA (gst_gram_counts), or null;
+                                 // then the DevAccum of an accumulating launch
 };
+GST_HOST_DEVICE inline DevAccum* accum_desc(unsigned long long* gram_cnt) {
+  return reinterpret_cast<DevAccum*>(gram_cnt + 2);
+}
 struct DevRec {
   double *x, *b, *z, *alpha, *pout, *theta, *nu;
   int nrec;

@@ -167,6 +167,7 @@ enum LargeKernel : int {
   LK_HYPER_REG8, LK_HYPER_REG16, LK_HYPER0, LK_HYPER1, LK_HYPER2, LK_HYPER_ECR6, LK_HYPER_ECR8,
   LK_BTM,
   LK_TOA_SMALL, LK_TOA,                               // toa_class 0, 1
+  LK_ACCUM,                                           // lg_accum (launched after lg_record's place)
   LK_COUNT
 };
 // The hyper kernel of a dataset: the one place that maps its class to a kernel
@@ -204,8 +205,10 @@ struct LargePlan {
 
 // mds: the batch's datasets (their integers only); debug: GST_DEBUG_*; rec_on: records are
 // written (record_every > 0, not eval_only).  eval_only: one pass up to the hyper launches.
+// acc_on: posterior sums are set (gst_set_accum; never with eval_only or GST_STAGE_GRAM):
+// lg_accum follows lg_record's place; the host skips it on sweeps before from_sweep.
 inline LargePlan plan_large(const DevModel* mds, int nd, int debug, int C, unsigned mask,
-                            bool eval_only, bool rec_on) {
+                            bool eval_only, bool rec_on, bool acc_on = false) {
   LargePlan p;
   const DevModel& h = mds[0];
   const int force = (debug & GST_DEBUG_LARGE_HYPER) ? 1 : 0;
@@ -253,6 +256,8 @@ inline LargePlan plan_large(const DevModel* mds, int nd, int debug, int C, unsig
       l.kind = GST_K_TB, l.gx = p.ys / 64, l.gy = chains(64 * TB_CG);
     } else if (k == LK_RECORD) {
       l.kind = GST_K_RECORD, l.record = true;
+    } else if (k == LK_ACCUM) {
+      l.kind = GST_K_ACCUM;
     } else if (k <= LK_WHITE) {
       l.kind = GST_K_WHITE, l.kclass = k - LK_WHITE_WAVE;
       l.block = k == LK_WHITE_WAVE ? TBLK_WAVE : (k == LK_WHITE_SMALL ? TBLK_SMALL : TBLK);
@@ -285,9 +290,10 @@ inline LargePlan plan_large(const DevModel* mds, int nd, int debug, int C, unsig
     for (int k = k0; k <= k1; ++k)
       if (on[k]) add(p.sweep, k, floor_pass);
   };
-  // One sweep = record, white, gram, tmelim, hyper, btm, tb, toa launches (gst_large.hpp)
+  // One sweep = record, accum, white, gram, tmelim, hyper, btm, tb, toa launches (gst_large.hpp)
   add(p.prologue, LK_TB);   // y = r - T b for the current b
   if (rec_on) add(p.sweep, LK_RECORD);
+  if (acc_on) add(p.sweep, LK_ACCUM);
   add_range(LK_WHITE_WAVE, LK_WHITE);
   if ((mask & (6u | GST_STAGE_GRAM)) || eval_only) {
     // one event pair around the Gram launches (each kernel skips the other's chains)

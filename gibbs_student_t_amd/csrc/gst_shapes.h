@@ -45,10 +45,11 @@ typedef void (*kfn_t)(const DevModel*, const DevState, const DevRec, const DevTa
 
 // tape: parity mode (4 chains per workgroup); wpb: chains per workgroup (4, or 2 / 1 for
 // sampling launches with fewer chains than fill every SIMD); occ2: the two-chains-per-SIMD
-// build (256 registers per lane); pair: two waves per chain (one chain per workgroup)
+// build (256 registers per lane); pair: two waves per chain (one chain per workgroup); acc:
+// the instance that keeps the posterior sums (gst_set_accum)
 #define GST_PICK_NAME(mt, ns, k0, ra, gen) pick_##mt##_##ns##_##k0##_##ra##_##gen
 #define GST_DECLARE_PICK(mt, ns, k0, ra, gen) \
-  kfn_t GST_PICK_NAME(mt, ns, k0, ra, gen)(bool tape, int wpb, bool occ2, bool pair);
+  kfn_t GST_PICK_NAME(mt, ns, k0, ra, gen)(bool tape, int wpb, bool occ2, bool pair, bool acc);
 GST_SHAPES(GST_DECLARE_PICK)
 #undef GST_DECLARE_PICK
 

@@ -16,6 +16,8 @@ from .model import df_tables, hyper_white_indices
 MODEL_CODES = {"gaussian": _abi.GST_MODEL_GAUSSIAN, "t": _abi.GST_MODEL_T,
                "mixture": _abi.GST_MODEL_MIXTURE, "vvh17": _abi.GST_MODEL_VVH17}
 STATE_KEYS = ("x", "b", "z", "alpha", "pout", "theta", "nu")
+# gst_accum's buffers, in the struct's order
+ACCUM_KEYS = ("z_sum", "pout_sum", "alpha_sum", "b_sum", "b_sq", "count")
 
 
 def _torch():
@@ -149,6 +151,7 @@ class NativeSampler:
         self.C = 0
         self.state = None
         self.dataset = None
+        self._accum = None
 
     def set_waves(self, waves="auto"):
         """Waves per chain of the persistent path's sampling launches (gst_set_waves):
@@ -227,6 +230,48 @@ class NativeSampler:
         shapes = {"x": (self.P,), "b": (self.m,), "z": (self.n,), "alpha": (self.n,),
                   "pout": (self.n,), "theta": (), "nu": ()}
         return {k: torch.empty((self.C, nrec) + shapes[k], **f64) for k in keys}
+
+    # ---- posterior sums (gst_set_accum) ----------------------------------------------
+    def _accum_shapes(self):
+        return {"z_sum": (self.C, self.n), "pout_sum": (self.C, self.n),
+                "alpha_sum": (self.C, self.n), "b_sum": (self.C, self.m),
+                "b_sq": (self.C, self.m), "count": (self.C,)}
+
+    def alloc_accum(self, keys=ACCUM_KEYS):
+        """Zeroed device tensors for the posterior sums: ``z_sum`` / ``pout_sum`` /
+        ``alpha_sum`` [C, n], ``b_sum`` / ``b_sq`` [C, m] (float64) and ``count`` [C]
+        (int64).  Pass the dict (or a subset of it) to ``set_accum``."""
+        torch = _torch()
+        shapes = self._accum_shapes()
+        unknown = [k for k in keys if k not in shapes]
+        if unknown:
+            raise ValueError(f"unknown accumulator(s) {unknown}; choose from {ACCUM_KEYS}")
+        return {k: torch.zeros(shapes[k], device=self.tdev,
+                               dtype=torch.int64 if k == "count" else torch.float64)
+                for k in keys}
+
+    def set_accum(self, acc: dict, from_sweep: int = 0):
+        """Every later ``sweep`` adds the state at the start of each of its sweeps with global
+        index ``sweep0 + i >= from_sweep`` into ``acc`` (tensors from ``alloc_accum``; missing
+        keys are skipped), whatever ``record_every`` is, until ``clear_accum``.  The sampler
+        keeps ``acc`` referenced while it is set."""
+        torch = _torch()
+        shapes = self._accum_shapes()
+        for k, t in acc.items():
+            want = torch.int64 if k == "count" else torch.float64
+            if k not in shapes or t.dtype != want or not t.is_contiguous() \
+                    or t.device != self.tdev or tuple(t.shape) != shapes[k]:
+                raise ValueError(f"accumulator {k!r}: need a contiguous {want} tensor of shape "
+                                 f"{shapes.get(k)} on {self.tdev} (alloc_accum)")
+        ptr = lambda k: ct.c_void_p(acc[k].data_ptr()) if k in acc else None  # noqa: E731
+        a = _abi.Accum(*(ptr(k) for k in ACCUM_KEYS), int(from_sweep))
+        _abi.check(self.lib, self.lib.gst_set_accum(self.ctx, ct.byref(a)), "gst_set_accum")
+        self._accum = acc
+
+    def clear_accum(self):
+        """Stop accumulating (launches already queued on the stream still add)."""
+        _abi.check(self.lib, self.lib.gst_set_accum(self.ctx, None), "gst_set_accum")
+        self._accum = None
 
     # ---- launches ------------------------------------------------------------------
     def stream_ptr(self):

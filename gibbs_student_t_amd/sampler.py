@@ -3,7 +3,9 @@
 Same constructor, same public methods and attributes; every sweep runs on the GPU through
 libgst.so.  Extra keyword-only options: ``nchains`` (independent chains batched on the GPU;
 chain arrays gain a leading chain axis when > 1), ``seed`` (Philox key), ``device``,
-``record_every`` (thin the chain arrays) and ``chunk`` (sweeps per kernel launch).
+``record_every`` (thin the chain arrays) and ``chunk`` (sweeps per kernel launch);
+``sample`` takes ``record`` (which chain arrays to keep), ``accumulate`` and ``burn`` (posterior
+sums kept on the device, left in ``self.post``: post.PosteriorSums).
 
 Differences from the reference, all documented in DESIGN.md:
 * ``update_b`` recomputes T^T N^-1 T from the current state; the reference reuses whatever
@@ -67,6 +69,7 @@ class Gibbs:
         self._cfg = dict(cfg, exact_bdraw=bool(exact_bdraw))
         self._x_all = None
         self._counter_at_sample = None      # Philox counter when sample() last returned
+        self.post = None                    # PosteriorSums of the last sample(accumulate=True)
         self._native = NativeSampler(pta, cfg, device)
         self._native.set_debug(exact_bdraw=exact_bdraw)
         self._native.alloc(C)
@@ -199,47 +202,66 @@ class Gibbs:
         return self._ret(self._stage(xs, _abi.STAGE_DF)["nu"])
 
     # ---- the sampler (gibbs.py:342-385) ----------------------------------------------------
-    def sample(self, xs, niter=10000):
+    def sample(self, xs, niter=10000, *, record=None, accumulate=False, burn=0):
+        """gibbs.py:342-385.  ``record``: the chain arrays to keep, a subset of ("x", "b",
+        "z", "alpha", "pout", "theta", "nu") (default: all, as the reference); an omitted array
+        is allocated neither on the host nor on the device, is not copied, and its attribute
+        (``zchain``, ...) is None.  ``accumulate``: keep the posterior sums of this call's
+        sweeps on the device, from its sweep ``burn`` on and on every sweep whatever
+        ``record_every`` is, and leave them in ``self.post`` (post.PosteriorSums); the sums of
+        successive calls merge with ``+``.  With both, a long run of a large pulsar gets its
+        outlier probabilities without any per-TOA chain array."""
         C, P = self.nchains, len(self.params)
         n, mcols = len(self._residuals), self._b_all.shape[1]
         every = max(1, self.record_every)
         nrec = (niter + every - 1) // every
         lead = () if C == 1 else (C,)
-        self.chain = np.zeros(lead + (nrec, P))
-        self.bchain = np.zeros(lead + (nrec, mcols))
-        self.thetachain = np.zeros(lead + (nrec,))
-        self.zchain = np.zeros(lead + (nrec, n))
-        self.alphachain = np.zeros(lead + (nrec, n))
-        self.poutchain = np.zeros(lead + (nrec, n))
-        self.dfchain = np.zeros(lead + (nrec,))
-        outs = {"x": self.chain, "b": self.bchain, "theta": self.thetachain,
-                "z": self.zchain, "alpha": self.alphachain, "pout": self.poutchain,
-                "nu": self.dfchain}
+        keys = STATE_KEYS if record is None else tuple(record)
+        unknown = [k for k in keys if k not in STATE_KEYS]
+        if unknown:
+            raise ValueError(f"record: unknown array(s) {unknown}; choose from {STATE_KEYS}")
+        tails = {"x": (nrec, P), "b": (nrec, mcols), "theta": (nrec,), "z": (nrec, n),
+                 "alpha": (nrec, n), "pout": (nrec, n), "nu": (nrec,)}
+        outs = {k: np.zeros(lead + tails[k]) for k in keys}
+        self.chain, self.bchain, self.thetachain = outs.get("x"), outs.get("b"), outs.get("theta")
+        self.zchain, self.alphachain = outs.get("z"), outs.get("alpha")
+        self.poutchain, self.dfchain = outs.get("pout"), outs.get("nu")
         self._push(self._xs_all(xs))
-        chunk = max(every, (self.chunk // every) * every)
-        tstart = time.time()
-        done, ri = 0, 0
-        while done < niter:
-            k = min(chunk, niter - done)
-            kr = (k + every - 1) // every
-            recs = self._native.alloc_records(kr)
-            self._native.sweep(k, records=recs, record_every=every, seed=self.seed,
-                               sweep0=self._sweep_counter)
-            self._sweep_counter += k
-            for key in STATE_KEYS:
-                host = recs[key].cpu().numpy()
-                if C == 1:
-                    outs[key][ri:ri + kr] = host[0]
-                else:
-                    outs[key][:, ri:ri + kr] = host
-            done += k
-            ri += kr
-            if self.verbose:
-                sys.stdout.write("\r")
-                sys.stdout.write("Finished %g percent in %g seconds." %
-                                 (done / niter * 100, time.time() - tstart))
-                sys.stdout.flush()
+        acc = None
+        if accumulate:
+            acc = self._native.alloc_accum()
+            self._native.set_accum(acc, from_sweep=self._sweep_counter + int(burn))
+        try:
+            chunk = max(every, (self.chunk // every) * every)
+            tstart = time.time()
+            done, ri = 0, 0
+            while done < niter:
+                k = min(chunk, niter - done)
+                kr = (k + every - 1) // every
+                recs = self._native.alloc_records(kr, keys) if keys else None
+                self._native.sweep(k, records=recs, record_every=every, seed=self.seed,
+                                   sweep0=self._sweep_counter)
+                self._sweep_counter += k
+                for key in keys:
+                    host = recs[key].cpu().numpy()
+                    if C == 1:
+                        outs[key][ri:ri + kr] = host[0]
+                    else:
+                        outs[key][:, ri:ri + kr] = host
+                done += k
+                ri += kr
+                if self.verbose:
+                    sys.stdout.write("\r")
+                    sys.stdout.write("Finished %g percent in %g seconds." %
+                                     (done / niter * 100, time.time() - tstart))
+                    sys.stdout.flush()
+        finally:
+            if accumulate:   # the stage methods and later sample() calls do not add to these sums
+                self._native.clear_accum()
         x = self._pull()
+        if accumulate:
+            from .post import PosteriorSums
+            self.post = PosteriorSums.from_device(acc)
         self._counter_at_sample = self._sweep_counter
         return x[0] if C == 1 else x
 

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GST_ABI_VERSION 6
+#define GST_ABI_VERSION 7
 
 /* Outlier model kind: Gibbs(model=...) (gibbs.py:9,32,187-226). */
 enum gst_outlier_model {
@@ -166,6 +166,31 @@ typedef struct gst_tape {
   int stride;
 } gst_tape;
 
+/* Posterior sums kept on the device (ABI 7): running sums of the per-TOA state and of b over
+ * the sweeps of every gst_sweep call, so that the products a long run ends in -- the outlier
+ * probabilities mean(z_t), mean(pout_t), mean(alpha_t) and the signal T mean(b)
+ * (gibbs_likelihood.ipynb: zchain.mean(axis=0) > 0.9, poutchain / alphachain means,
+ * T @ bchain) -- need no per-TOA chain records.  DEVICE pointers owned by the caller, fp64
+ * (count: 64-bit integers), indexed by launch-local chain like gst_state, row stride nmax for
+ * the per-TOA sums; the caller zeroes them.  Any pointer may be NULL to skip that sum.
+ * While set, every sweep i of every gst_sweep call with sweep0 + i >= from_sweep adds the
+ * state at the START of the sweep -- the values a record of that sweep holds -- and
+ * increments count[c], on every sweep whatever record_every is; sums carry over from one
+ * launch to the next.  Each element is added by one owner in sweep order as a plain
+ * sum = sum + v (b_sq: sum + v * v, which may be fused), so sum[c][t] is bitwise the
+ * sequential sum of the records.  Entries t >= n of a chain's dataset are never touched;
+ * chains that a path does not run (status bit 2 on the persistent path) keep count 0.
+ * gst_eval_lnlike and GST_STAGE_GRAM launches never accumulate. */
+typedef struct gst_accum {
+  double* z_sum;      /* [C][nmax]  sum of z_t over counted sweeps */
+  double* pout_sum;   /* [C][nmax]  sum of pout_t */
+  double* alpha_sum;  /* [C][nmax]  sum of alpha_t */
+  double* b_sum;      /* [C][m]     sum of b_j */
+  double* b_sq;       /* [C][m]     sum of b_j^2 */
+  long long* count;   /* [C]        counted sweeps */
+  long long from_sweep; /* global sweep index (sweep0 + i) of the first counted sweep */
+} gst_accum;
+
 int gst_version(void);
 int gst_tape_stride(int n, int m);
 int gst_last_error(char* buf, size_t len);
@@ -212,6 +237,10 @@ int gst_sweep(void* ctx, const gst_state* state, const gst_records* rec,
  * using chain k's b, z, alpha from `state` (x from state->x). */
 int gst_eval_lnlike(void* ctx, const gst_state* state, int nchains, double* out_white,
                     double* out_hyper, void* stream);
+
+/* Posterior sums (gst_accum above): *acc is copied; NULL switches accumulation off.  Takes
+ * effect from the next gst_sweep call, in stream order with it. */
+int gst_set_accum(void* ctx, const gst_accum* acc);
 
 int gst_sync(void* ctx, void* stream);
 
@@ -285,7 +314,9 @@ int gst_set_debug(void* ctx, int flags);
  * milliseconds) and launches[k] for kernel kinds k < nkinds (enum gst_kernel_kind). */
 enum gst_kernel_kind {
   GST_K_RECORD = 0, GST_K_WHITE = 1, GST_K_GRAM = 2, GST_K_TMELIM = 3,
-  GST_K_HYPER = 4, GST_K_BTM = 5, GST_K_TB = 6, GST_K_TOA = 7, GST_K_COUNT = 8
+  GST_K_HYPER = 4, GST_K_BTM = 5, GST_K_TB = 6, GST_K_TOA = 7,
+  GST_K_ACCUM = 8, /* lg_accum: the posterior sums (ABI 7) */
+  GST_K_COUNT = 9
 };
 int gst_set_timing(void* ctx, int on);
 int gst_kernel_times(void* ctx, double* ms, int* launches, int nkinds);

@@ -1,5 +1,6 @@
 // Stand-alone driver of the launch planner (csrc/gst_plan.h) for tests/test_plan.py:
 //   plan_dump large C mask debug eval_only rec_on DATASET...
+//   plan_dump large_acc ...   the same call with the posterior sums on (plan_large's acc_on)
 //       DATASET = npad,mp,nf,nec,ntm,ntm_pad,raug,ec_disjoint,gx_nt
 //       prints "error: <message>", or per launch
 //       "<prologue|sweep> <kernel> <kind> <gx> <gy> <block> <lds bytes> <kclass> <floor> <ev> <record>"
@@ -18,9 +19,9 @@ static const char* kNames[gst::LK_COUNT] = {
     "gram_ec<3>", "gram_ec<4>", "gram_small<1>", "gram_small<2>", "gram_small<3>",
     "gram_small<4>", "gram_small<5>", "gram_small<6>", "gram", "tmelim", "hyper_reg<8>",
     "hyper_reg<16>", "hyper<0>", "hyper<1>", "hyper<2>", "hyper_ecr<6,46>", "hyper_ecr<8,62>",
-    "btm", "toa<256>", "toa<1024>"};
+    "btm", "toa<256>", "toa<1024>", "accum"};
 static const char* kKinds[GST_K_COUNT] = {"RECORD", "WHITE", "GRAM", "TMELIM", "HYPER", "BTM",
-                                          "TB", "TOA"};
+                                          "TB", "TOA", "ACCUM"};
 
 static void dump(const char* list, const std::vector<gst::Launch>& v) {
   for (const gst::Launch& l : v)
@@ -30,7 +31,8 @@ static void dump(const char* list, const std::vector<gst::Launch>& v) {
 
 int main(int argc, char** argv) {
   auto num = [&](int i) { return (int)std::strtol(argv[i], nullptr, 0); };
-  if (argc >= 8 && !std::strcmp(argv[1], "large")) {
+  const bool acc_on = argc >= 2 && !std::strcmp(argv[1], "large_acc");
+  if (argc >= 8 && (acc_on || !std::strcmp(argv[1], "large"))) {
     std::vector<gst::DevModel> mds;
     for (int i = 7; i < argc; ++i) {
       gst::DevModel md{};
@@ -40,7 +42,7 @@ int main(int argc, char** argv) {
       mds.push_back(md);
     }
     const gst::LargePlan p = gst::plan_large(mds.data(), (int)mds.size(), num(4), num(2),
-                                             (unsigned)num(3), num(5) != 0, num(6) != 0);
+                                             (unsigned)num(3), num(5) != 0, num(6) != 0, acc_on);
     if (!p.error.empty()) {
       std::printf("error: %s\n", p.error.c_str());
       return 0;
