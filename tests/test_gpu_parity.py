@@ -348,6 +348,38 @@ def test_failed_factor_never_draws_b(path):
     ns.close()
 
 
+@pytest.mark.parametrize("name,debug", [("scaled_beta_fixed", {}),
+                                        ("beta_fixed", {"large_hyper": True}),
+                                        ("ebig_beta_fixed", {"large_hyper": True}),
+                                        ("mb_beta_fixed", {"epochs_lds": True}),
+                                        ("mb_beta_fixed", {})],
+                         ids=["hyper_reg16", "hyper0", "hyper1", "hyper2", "hyper_ecr"])
+def test_failed_factor_never_draws_b_large_variants(name, debug):
+    """The same on every other hyper kernel of the large path: lg_hyper_reg<16> (scaled),
+    lg_hyper<0> (its own copy of the MH loop), the blocked lg_hyper<1> (ebig), the epochs-first
+    lg_hyper<2> and lg_hyper_ecr<6,46> (mb).  Every loop on their failed-pivot paths has a fixed
+    trip count (pivots only enter as data), so NaN / negative pivots end in the flags."""
+    ref = load_ref(name)
+    s0 = sweep_state(ref, 0)
+    ns = _native(ref, 1, "large")
+    ns.set_debug(**debug)
+    alpha = np.full_like(s0["alpha"], -1.0)            # N = alpha^z N0 < 0 where z = 1
+    b0 = np.linspace(-1e-7, 1e-7, ns.m)[None]
+    ns.set_state(x=ref["xs"][None], b=b0, z=np.ones_like(s0["z"])[None], alpha=alpha[None],
+                 pout=s0["pout"][None], theta=np.array([s0["theta"]]),
+                 nu=np.array([s0["nu"]]))
+    rows = pack_tape(ref["tape"], [0], ns.n, ns.m, ns.stride)
+    for step in range(10):
+        rows[0, _abi.TAPE_HYPER + 4 * step + 2] = 1e6     # jump far outside the prior box
+    tape = torch.as_tensor(rows[:, None, :]).to(ns.tdev).contiguous()
+    ns.sweep(1, mask=_abi.STAGE_HYPER | _abi.STAGE_B | _abi.STAGE_B_FORCE, tape=tape)
+    out = ns.get_state()
+    assert out["status"][0] & 2 and out["status"][0] & 1
+    np.testing.assert_array_equal(out["b"], b0)
+    np.testing.assert_array_equal(out["x"][0], ref["xs"])
+    ns.close()
+
+
 @pytest.mark.parametrize("path", PATHS)
 def test_philox_mode_runs_and_moves(path):
     ref = load_ref("beta_fixed")
