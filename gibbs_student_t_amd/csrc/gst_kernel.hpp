@@ -43,7 +43,8 @@ typedef __attribute__((address_space(1))) double GDouble;
 // loads; the 8 owner lanes (q == column residue) write it.  Row stride MT = 10 doubles puts
 // the 8 p-rows of a 128-bit read in distinct bank groups (80 B apart).
 
-// diagnostic builds: slots 0-15, 19-23 cycle sums (tools/stage_profile.py), 16-18 event counts
+// diagnostic builds: slots 0-15, 19-27 cycle sums (tools/stage_profile.py), 16-18 event counts
+// (26 / 27, one-wave hyper loop: end of chol_stats -> MH verdict, verdict -> next lnl_hyper)
 constexpr int GST_NSTAMP = 28;
 #ifdef GST_STAMPS
 #define GST_STAMP_DECL \
@@ -158,6 +159,20 @@ __device__ __forceinline__ double wave_sum(double v) {
   v += dpp<DPP_ROR4>(v);
   v += dpp<DPP_ROR8>(v);
   return (rdlane(v, 0) + rdlane(v, 16)) + (rdlane(v, 32) + rdlane(v, 48));
+}
+
+// The same for an int (exact in any order): the DPP adds, then the four row sums.
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+  v += dpp_i<DPP_XOR1>(v);
+  v += dpp_i<DPP_XOR2>(v);
+  v += dpp_i<DPP_ROR4>(v);
+  v += dpp_i<DPP_ROR8>(v);
+  return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
+         (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
 }
 
 __device__ __forceinline__ double wave_max(double v) {
@@ -848,7 +863,7 @@ __device__ __forceinline__ void chol_stats(CholCtx& cc) {
   mm *= dpp<DPP_ROR4>(mm);
   mm *= dpp<DPP_ROR8>(mm);
   cc.mant = (rdlane(mm, 0) * rdlane(mm, 16)) * (rdlane(mm, 32) * rdlane(mm, 48));
-  cc.expo = (int)wave_sum((double)ee);
+  cc.expo = wave_sum_i(ee);
   cc.quad = wave_sum(qd);
   cc.fail = __ballot(f) != 0ull ? 1 : 0;
 }
@@ -1072,16 +1087,21 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     hefc = md.efac_const;
   }
   auto lnprior = [&](const double (&xq)[PX]) __attribute__((always_inline)) -> double {
-    bool in = true;
+    // Branch-free, and every bound read before the first compare: the short-circuit form
+    // compiled to a cascade of branches in which each bound's scalar load was issued and
+    // waited for (with every LDS access in flight) in turn, up to 2 P + 1 round trips per call
+    // (pmin / pmax have PMAX >= PX entries: the ones past P are read and ignored)
+    double lo[PX], hi[PX];
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
-      if (OCC == 1) {
-        if (j < P) in = in && (xq[j] >= hpmin[j]) && (xq[j] <= hpmax[j]);
-      } else {
-        if (j < P) in = in && (xq[j] >= md.pmin[j]) && (xq[j] <= md.pmax[j]);
-      }
+      lo[j] = OCC == 1 ? hpmin[j] : md.pmin[j];
+      hi[j] = OCC == 1 ? hpmax[j] : md.pmax[j];
     }
-    return in ? (OCC == 1 ? hlp : md.lp_sum) : -INFINITY;
+    const double lp = OCC == 1 ? hlp : md.lp_sum;
+    bool in = true;
+#pragma unroll
+    for (int j = 0; j < PX; ++j) in = in & ((j >= P) | ((xq[j] >= lo[j]) & (xq[j] <= hi[j])));
+    return in ? lp : -INFINITY;
   };
 
   auto efac2_of = [&](const double (&xq)[PX]) __attribute__((always_inline)) -> double {
@@ -1581,8 +1601,12 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
   auto lnl_hyper = [&](const double (&xq)[PX], int& failed) __attribute__((always_inline)) -> double {
     GST_COUNT(16)
     GST_SUB_BEGIN
-    const double lA = pget(xq, hidxA);
-    const double g = pget(xq, hidxg);
+    // the parameter indices as per-lane values: over a wave-uniform index pget's selects
+    // compiled to a cascade of scalar branches in front of every factorisation
+    int iA = hidxA, ig = hidxg;
+    asm("" : "+v"(iA), "+v"(ig));
+    const double lA = pget(xq, iA);
+    const double g = pget(xq, ig);
     // log phi_k = 2 lA ln10 - log(12 pi^2) + (g-3) log fyr - g log f_k + log df_k
     const double lc = 2.0 * lA * 2.302585092994045684 - hl12 + (g - 3.0) * hlfyr;
     // S0 first: its 36 LDS loads are in flight while phi^-1 is computed (exp)
@@ -1599,8 +1623,10 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
             f_live ? exp(-(lc - g * lfreq_l + ldf_l)) + fshift
                    : (geci >= 0 ? exp(-2.0 * pget(xq, geci) * 2.302585092994045684) + fshift : 1.0);
     } else {
-      if (lane < RA - hntmp)
-        phbuf[hntmp + lane] = f_live ? exp(-(lc - g * lfreq_l + ldf_l)) + fshift : 1.0;
+      // every lane takes the exp (it sat in an exec-masked region of its own; the dummy
+      // columns' lanes drop the value)
+      const double e = exp(-(lc - g * lfreq_l + ldf_l));
+      if (lane < RA - hntmp) phbuf[hntmp + lane] = f_live ? e + fshift : 1.0;
     }
     // phbuf doubles as the eliminations' junk rows: restore the one other entry read
     // below, the augmented row's (no prior on the residual column)
@@ -2079,6 +2105,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
                                           __HIP_MEMORY_SCOPE_AGENT);
       if (fail_tm) status |= 1;
       GST_STAMP(2)
+      GST_SUB_BEGIN
 #pragma unroll 1
       for (int step = pass ? NHYPER : first; step <= NHYPER; ++step) {
         fair_prio<OCC>(fair);
@@ -2103,6 +2130,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
         const double p1 = lnprior(qv);
         if (step >= 0 && step < NHYPER && p1 == -INFINITY) continue;
         int f1 = 0;
+        GST_SUB_END(27)
         const double l1 = lnl_hyper(qv, f1);
         if (step == NHYPER) {
           fb = f1;
@@ -2131,6 +2159,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
         } else {
           Lvalid = false;
         }
+        GST_SUB_END(26)
       }
       if (pass == 1 || eval_only || !redraw || fb || (st.debug & DEBUG_EXACT_BDRAW)) break;
       fshift = floor_shift(f_apr, lane, md.ntm, md.ntm_pad, md.ntm_pad + md.nf + (GEN ? md.nec : 0));

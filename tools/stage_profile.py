@@ -54,14 +54,19 @@ def main():
     tot = cyc[:, :7].sum(axis=1)
     print(f"C={C} S={S} waves={waves} kernel {ms:.2f} ms = {ms / S * 1e3:.1f} us/sweep; "
           f"stamped cycles/sweep/chain median {np.median(tot):.0f}")
+    # the hyper block's cycles outside every sub-stamp (7, 8, 19, 26, 27)
+    rest = cyc[:, 3] - cyc[:, [7, 8, 19, 26, 27]].sum(axis=1)
     for i, nm in enumerate(STAGES):
         print(f"  {nm:22s} {np.median(cyc[:, i]):10.0f} cyc  {np.median(cyc[:, i] / tot) * 100:5.1f} %")
 
     for i, nm in ((19, "(hyper: harvest + stats)"), (20, "(record: MH variates)"),
                   (21, "(white: class sums)"), (22, "(white: lane lnL tree)"),
-                  (23, "(outlier: theta)"), (24, "(outlier: z)"), (25, "(outlier: alpha)")):
+                  (23, "(outlier: theta)"), (24, "(outlier: z)"), (25, "(outlier: alpha)"),
+                  (26, "(hyper: stats -> verdict)"), (27, "(hyper: verdict -> lnL)")):
         print(f"  {nm:22s} {np.median(cyc[:, i]):10.0f} cyc  "
               f"{np.median(cyc[:, i] / tot) * 100:5.1f} %")
+    print(f"  {'(hyper: unattributed)':22s} {np.median(rest):10.0f} cyc  "
+          f"{np.median(rest / tot) * 100:5.1f} %")
     for i, nm in ((16, "red-noise lnL evaluations"), (17, "two-wave rounds"),
                   (18, "accepted red-noise proposals")):
         print(f"  {nm:30s} {cyc[:, i].mean():6.2f} per sweep")
