@@ -1272,11 +1272,18 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
 
   // SVD noise floor f of this sweep's b draw (floor_shift; 0 except on the floor redo)
   double fshift = 0.0;
+  // the low-rank Gram's descriptor pointers, read once for the launch (wave-uniform: scalar
+  // registers) like lnl_hyper's scalars below, not at every class and flagged TOA
+  const double* const hgcls = md.Gcls;
+  const double* const hcsig2 = md.csig2;
+  const int* const hcidx = md.cidx;
+  const GDouble* const htrow = (const GDouble*)md.Trow;
   // Gram: G = T_aug^T diag(1/N) T_aug on fp64 MFMA, then TM elimination -> S0.
   auto gram_and_tm = [&](const double (&xq)[PX]) __attribute__((always_inline)) {
     const double ef2 = efac2_of(xq);
     const double Q = exp(2.0 * pget(xq, md.idx_equad) * 2.302585092994045684);
     double sr = 0.0;
+    double wlane[NS];   // the lane's weights w_t = 1 / N_t (the low-rank Gram reads them by lane)
     LogProd lp;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -1295,6 +1302,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
         w = 1.0 / N;
       }
       vbuf[t] = w;
+      wlane[s] = w;
     }
     logdetN = wave_sum(lp.log_sum());
     rNr = wave_sum(sr);
@@ -1317,33 +1325,84 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
       nout += __popcll(__ballot(((zb & vmask) >> s) & 1u));
       big = big || ((((zb & vmask) >> s) & 1u) && al[s] > LR_ALPHA_MAX);
     }
-    if (md.Gcls && nout <= LR_MAX && !(st.debug & DEBUG_MFMA_GRAM) && __ballot(big) == 0ull) {
+    if (hgcls && nout <= LR_MAX && !(st.debug & DEBUG_MFMA_GRAM) && __ballot(big) == 0ull) {
       __hip_atomic_fetch_add(&gcnt[wv][0], lane == 0 ? 1u : 0u, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_WAVEFRONT);
+      // Every load of a class Gram is issued before the first is waited for, and class 0's land
+      // in L itself (in source order load, FMA, load, FMA each of the 55 loads was a memory
+      // round trip of its own: the compiler keeps that order).  The reciprocals c_k = 1 / N0_k
+      // are formed once per Gram, class u by lane u as in lnl_white, while class 0 is in
+      // flight; both loops below read them by lane.  Each operation and its operands are the
+      // serial form's (an FMA with a zero addend for class 0, the explicit fma of N0 that the
+      // serial form contracted to), so the chains are bitwise unchanged.
+      // The class arrays are read as lane rows (a buffer resource in scalar registers + the
+      // lane's byte offset): as 64-bit per-lane pointers they were one address pair per load
+      // in flight (or per launch-invariant address), spilled and reloaded one by one.  Reads
+      // past an array's end (lanes >= ncls, a ragged batch's missing TOA slots) return zero.
+      const LaneRows gcls = lane_rows(hgcls, hncls * NSL * 64, lane);
+      const LaneRows csr = lane_rows(hcsig2, hncls, lane);
+      const double cs2 = lr_load(csr, 0);
 #pragma unroll
-      for (int i = 0; i < SL(MT, 0); ++i) L[i] = 0.0;
+      for (int i = 0; i < NSL; ++i) L[i] = lr_load(gcls, 512 * i);
+      __builtin_amdgcn_sched_barrier(0);
+      const double cinv = 1.0 / (GEN ? gen_n0(xq, cs2, gcef, gceq) : fma(ef2, cs2, Q));
+      const double c0 = rdlane(cinv, 0);
+#pragma unroll
+      for (int i = 0; i < NSL; ++i) L[i] = fma(c0, L[i], 0.0);
+      if (hncls > 1) {
+        const __amdgpu_buffer_rsrc_t cir =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<int*>(hcidx), 0, npad * 4, 0x00020000);
+        int cls[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+          cls[s] = __builtin_amdgcn_raw_buffer_load_b32(cir, 4 * lane, 256 * s, 0);
 #pragma unroll 1
-      for (int k = 0; k < md.ncls; ++k) {
-        const double ck = 1.0 / (GEN ? cls_n0(xq, k) : ef2 * md.csig2[k] + Q);
-        const GDouble* gk = (const GDouble*)md.Gcls + (size_t)k * SL(MT, 0) * 64 + lane;
+        for (int k = 1; k < hncls; ++k) {
+          const double ck = rdlane(cinv, k);
+          const int gk = k * NSL * 512;   // class k's byte offset
+          // MT loads in flight per round: the temporaries stay below the flagged loop's rows
 #pragma unroll
-        for (int i = 0; i < SL(MT, 0); ++i) L[i] = fma(ck, gk[64 * i], L[i]);
+          for (int i0 = 0; i0 < NSL; i0 += MT) {
+            double g[MT];
+#pragma unroll
+            for (int i = i0; i < i0 + MT && i < NSL; ++i) g[i - i0] = lr_load(gcls, gk + 512 * i);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = i0; i < i0 + MT && i < NSL; ++i) L[i] = fma(ck, g[i - i0], L[i]);
+          }
+        }
+        // w_t - c_k(t) of the lane's own TOAs
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          double ck = c0;
+#pragma unroll
+          for (int u = 1; u < 8; ++u) ck = cls[s] == u ? rdlane(cinv, u) : ck;
+          wlane[s] = wlane[s] - ck;
+        }
+      } else {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) wlane[s] = wlane[s] - c0;
       }
-      // flagged TOAs, one rank-1 update each: c_k (1 / alpha_t - 1) = w_t - c_k, with the
-      // weight w_t = 1 / N_t the loop above left in vbuf
+      // flagged TOAs, one rank-1 update each: c_k (1 / alpha_t - 1) = w_t - c_k, formed above
+      // by the lane that holds the TOA's weight w_t = 1 / N_t.  Between two TOAs' row loads
+      // there is address arithmetic only: no load of the class, no division, no LDS read
 #pragma unroll 1
       for (int s = 0; s < NS; ++s) {
         unsigned long long bm = __ballot(((zb & vmask) >> s) & 1u);
+        int sv = s;   // a per-lane value: selects, not a cascade of scalar branches
+        asm("" : "+v"(sv));
+        double vs = wlane[0];
+#pragma unroll
+        for (int s2 = 1; s2 < NS; ++s2) vs = sv == s2 ? wlane[s2] : vs;
 #pragma unroll 1
         while (bm) {
-          const int t = 64 * s + __builtin_ctzll(bm);
+          const int tl = __builtin_ctzll(bm);
+          const int t = 64 * s + tl;
           bm &= bm - 1;
-          const int k = md.ncls > 1 ? md.cidx[t] : 0;
-          const double v = vbuf[t] - 1.0 / (GEN ? cls_n0(xq, k) : ef2 * md.csig2[k] + Q);
           // [T|r]_t at internal columns 8 r + p (row side) and 8 r + q (column side): each
           // lane's MT entries are contiguous in Trow ([t][i % 8][i / 8]), 128-bit loads
           typedef double v2_t __attribute__((ext_vector_type(2)));
-          const GDouble* tr = (const GDouble*)md.Trow + (size_t)t * 8 * MT;
+          const GDouble* tr = htrow + (size_t)t * 8 * MT;
           const __attribute__((address_space(1))) v2_t* trp =
               (const __attribute__((address_space(1))) v2_t*)(tr + MT * p);
           const __attribute__((address_space(1))) v2_t* trq =
@@ -1357,6 +1416,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
             tq_[r] = b[0];
             tq_[r + 1] = b[1];
           }
+          const double v = rdlane(vs, tl);
 #pragma unroll
           for (int r = 0; r < MT; ++r) {
             const double vr = v * tp_[r];
