@@ -13,6 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgst.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("gst.hip", "gst_inst.hip", "gst_shapes.h", "gst_sim.hpp",
                                             "gst_kernel.hpp", "gst_large.hpp", "philox.hpp",
+                                            "gst_wave.hpp", "gst_chol.hpp", "gst_draws.h",
                                             "gst_model.h", "gst_pack.h", "gst_plan.h")]
 HEADER = os.path.join(ROOT, "include", "gst.h")
 
@@ -75,7 +76,8 @@ def build(force: bool = False, verbose: bool = True, stamps: bool = False,
 
     # incremental (not for force=True): a unit is recompiled when its object is missing, older
     # than one of its sources, or was built with other flags (a .cmd file beside it)
-    kern_deps = [os.path.join(CSRC, f) for f in ("gst_kernel.hpp", "gst_model.h", "philox.hpp", "gst_shapes.h")]
+    kern_deps = [os.path.join(CSRC, f) for f in ("gst_kernel.hpp", "gst_wave.hpp", "gst_chol.hpp", "gst_draws.h",
+                                                 "gst_model.h", "philox.hpp", "gst_shapes.h")]
     deps = {"gst.hip": SOURCES + [HEADER],
             "gst_inst.hip": kern_deps + [os.path.join(CSRC, "gst_inst.hip"), HEADER]}
 

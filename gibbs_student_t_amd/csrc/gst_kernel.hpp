@@ -28,845 +28,13 @@
 
 #include <type_traits>
 
+#include "gst_chol.hpp"
+#include "gst_draws.h"
 #include "gst_model.h"
+#include "gst_wave.hpp"
 #include "philox.hpp"
 
 namespace gst {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-// a global-memory double: loads through it are global_load (a generic pointer read out of
-// DevModel compiles to flat_load, which also waits on the LDS counter)
-typedef __attribute__((address_space(1))) double GDouble;
-
-// The published column: colq[p][r] = row 8r+p of the column being eliminated, r fastest, so
-// a lane's row-side (p) and column-side (q) reads are contiguous in r and go as 128-bit LDS
-// loads; the 8 owner lanes (q == column residue) write it.  Row stride MT = 10 doubles puts
-// the 8 p-rows of a 128-bit read in distinct bank groups (80 B apart).
-
-// diagnostic builds: slots 0-15, 19-27 cycle sums (tools/stage_profile.py), 16-18 event counts
-// (26 / 27, one-wave hyper loop: end of chol_stats -> MH verdict, verdict -> next lnl_hyper)
-constexpr int GST_NSTAMP = 28;
-#ifdef GST_STAMPS
-#define GST_STAMP_DECL \
-  unsigned long long st_acc[GST_NSTAMP] = {0}, st_t0 = 0, st_s0 = 0;
-#define GST_SUB_BEGIN st_s0 = __builtin_amdgcn_s_memtime();
-#define GST_COUNT(i) st_acc[i] += 1;
-#define GST_SUB_END(i)                                            \
-  {                                                               \
-    const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); \
-    st_acc[i] += t1_ - st_s0;                                     \
-    st_s0 = t1_;                                                  \
-  }
-#define GST_STAMP_START st_t0 = __builtin_amdgcn_s_memtime();
-#define GST_STAMP(i)                                              \
-  {                                                               \
-    const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); \
-    st_acc[i] += t1_ - st_t0;                                     \
-    st_t0 = t1_;                                                  \
-  }
-#define GST_STAMP_FLUSH                                             \
-  if (md.stamps && lane == 0)                                       \
-    for (int i_ = 0; i_ < GST_NSTAMP; ++i_) md.stamps[(size_t)c * GST_NSTAMP + i_] += st_acc[i_];
-#else
-#define GST_SUB_BEGIN
-#define GST_COUNT(i)
-#define GST_SUB_END(i)
-#define GST_STAMP_DECL
-#define GST_STAMP_START
-#define GST_STAMP(i)
-#define GST_STAMP_FLUSH
-#endif
-
-__device__ __forceinline__ double rdlane(double v, int lane) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// Two chains share each SIMD in the OCC = 2 build, and the SIMD's arbiter issues the older
-// wave first: the chain that arrived second ran ~27% slower per sweep than its partner and
-// every launch ended with it (tools/chain_pairs.py).  Priority turns fix that:
-//  * progress rule (the host passes st.prog): each chain counts its sweep into a
-//    launch-wide counter (one atomic per chain-sweep, its return value consumed a sweep
-//    later); a chain that has done fewer sweeps than the launch average holds the higher
-//    issue priority;
-//  * the first sweep of a launch, and launches without st.prog: time slices of 2^15 clocks
-//    by wave-slot parity (slot-parity-1 waves hold the higher priority kPrioShare / 8
-//    of the time).
-// Checked at the sweep, MH-step and stage boundaries (the clock read waits only there).
-constexpr unsigned kPrioShare = 5;  // 4: 8.50 M, 5: 8.65 M, 6: 8.38 M chain-sweeps/s (age favours the older wave)
-__device__ __forceinline__ unsigned wave_slot_parity() {
-  return __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4) & 1u;  // HW_REG_HW_ID.WAVE_ID
-}
-struct Fair {
-  unsigned slot;            // wave-slot parity
-  int behind;               // progress rule: 1 = behind the launch average, -1 = no rule
-};
-template <int OCC>
-__device__ __forceinline__ void fair_prio(const Fair& f) {
-  if constexpr (OCC == 2) {
-    bool high;
-    if (f.behind >= 0) {
-      high = f.behind != 0;
-    } else {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      high = ((((unsigned)(t >> 15)) & 7u) < kPrioShare) == (f.slot != 0u);
-    }
-    if (high)
-      __builtin_amdgcn_s_setprio(1);
-    else
-      __builtin_amdgcn_s_setprio(0);
-  }
-}
-
-// Per-lane fp64 rows in global memory addressed as (wave-uniform buffer resource, this
-// lane's byte offset, a constant byte offset in an SGPR): every access needs only the one
-// lane-offset VGPR, where 64-bit per-lane pointers (base + lane + 4 KB multiples) would each
-// hold two VGPRs across the sweep loop -- and get spilled, then reloaded one after another.
-struct LaneRows {
-  __amdgpu_buffer_rsrc_t rs;
-  int vo;
-};
-__device__ __forceinline__ LaneRows lane_rows(const double* base, int doubles, int lane) {
-  return {__builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base), 0, doubles * 8, 0x00020000),
-          lane * 8};
-}
-__device__ __forceinline__ double lr_load(const LaneRows& b, int byte_off) {
-  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(b.rs, b.vo, byte_off, 0));
-}
-__device__ __forceinline__ void lr_store(const LaneRows& b, int byte_off, double v) {
-  typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, v), b.rs, b.vo, byte_off, 0);
-}
-
-// Cross-lane moves within a 16-lane row by DPP (VALU speed, no LDS traffic).
-template <int CTRL>
-__device__ __forceinline__ double dpp(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_ROR4 = 0x124, DPP_ROR8 = 0x128;
-
-// Sum over the wave: quad butterflies + row rotations give every lane its 16-lane row sum,
-// then the four row sums are combined in a fixed order from lanes 0/16/32/48, so the result
-// is bitwise identical (uniform) in every lane.
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp<DPP_XOR1>(v);
-  v += dpp<DPP_XOR2>(v);
-  v += dpp<DPP_ROR4>(v);
-  v += dpp<DPP_ROR8>(v);
-  return (rdlane(v, 0) + rdlane(v, 16)) + (rdlane(v, 32) + rdlane(v, 48));
-}
-
-// The same for an int (exact in any order): the DPP adds, then the four row sums.
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-  v += dpp_i<DPP_XOR1>(v);
-  v += dpp_i<DPP_XOR2>(v);
-  v += dpp_i<DPP_ROR4>(v);
-  v += dpp_i<DPP_ROR8>(v);
-  return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
-         (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-  v = fmax(v, dpp<DPP_XOR1>(v));
-  v = fmax(v, dpp<DPP_XOR2>(v));
-  v = fmax(v, dpp<DPP_ROR4>(v));
-  v = fmax(v, dpp<DPP_ROR8>(v));
-  return fmax(fmax(rdlane(v, 0), rdlane(v, 16)), fmax(rdlane(v, 32), rdlane(v, 48)));
-}
-
-// ---- SVD noise floor of the b draw (include/gst.h gst_sweep; oracle Oracle.floor_shift) ----
-// The reference draws b through sl.svd(Sigma) (gibbs.py:169-171).  When Sigma's smallest
-// eigenvalues lie below ~eps ||Sigma|| (vvh17's all-outlier start, alpha = 1e10: cond ~ 1e22,
-// while Sigma diagonally scaled is well conditioned) LAPACK returns them at its own rounding
-// floor, ~0.3-2 x 2^-52 s_max, so its draw is in effect one from Sigma + f I -- which is what
-// lets the reference's chains leave that state within ~100 sweeps (the exact draw stays there
-// for thousands).  The b draw reproduces it: when the smallest pivot of
-// the factor over the real columns is below FLOOR_GATE = 2^-52 x the largest (the pivot ratio
-// below which LAPACK's SVD resolves those eigenvalues no longer: above it the reference's SVD
-// mean agrees with the exact mean to ~1e-6), b is drawn exactly from
-// Sigma + f I with f = FLOOR_C 2^-52 x the largest pivot; every other draw is the exact one.
-// Each floor draw sets status bit 4 and adds 1 to the floor-draw count in bits 8..30.
-constexpr double FLOOR_GATE = 0x1p-52;
-#ifndef GST_FLOOR_C
-#define GST_FLOOR_C 0.75  // oracle/gibbs_oracle.py FLOOR_C (tools/vvh17_escape.py calibrates it)
-#endif
-constexpr double FLOOR_C = GST_FLOOR_C;
-constexpr int STATUS_FLOOR = 16;
-constexpr int STATUS_FLOOR_COUNT = 256;   // one floor draw, counted in bits 8..30
-
-// Smallest / largest pivot over the real columns of a factor whose pivot of internal column
-// j = 64 sl + lane is apr[sl]; real columns are [0, ntm) and [f0, f1) (the rest are unit-prior
-// pads).  Wave-uniform.
-__device__ __forceinline__ void pivot_range(const double (&apr)[2], int lane, int ntm, int f0,
-                                            int f1, double& mn, double& mx) {
-  mx = 0.0;
-  mn = INFINITY;
-#pragma unroll
-  for (int sl = 0; sl < 2; ++sl) {
-    const int j = 64 * sl + lane;
-    const bool real = j < ntm || (j >= f0 && j < f1);
-    mx = real ? fmax(mx, apr[sl]) : mx;
-    mn = real ? fmin(mn, apr[sl]) : mn;
-  }
-  mx = wave_max(mx);
-  mn = -wave_max(-mn);
-}
-__device__ __forceinline__ double floor_of(double mn, double mx) {
-  return mn < FLOOR_GATE * mx ? FLOOR_C * 0x1p-52 * mx : 0.0;
-}
-__device__ __forceinline__ double floor_shift(const double (&apr)[2], int lane, int ntm, int f0,
-                                              int f1) {
-  double mn, mx;
-  pivot_range(apr, lane, ntm, f0, f1, mn, mx);
-  return floor_of(mn, mx);
-}
-
-// Sum over p (lane bits 3..5) of the lanes with q == qq (lane = 8p + q), uniform result.
-__device__ __forceinline__ double col_sum(double v, int qq) {
-  v += dpp<DPP_ROR8>(v);  // (l + 8) mod 16 == l ^ 8
-  return (rdlane(v, qq) + rdlane(v, qq + 16)) + (rdlane(v, qq + 32) + rdlane(v, qq + 48));
-}
-
-// 1/sqrt(a): hardware estimate + two Newton steps (full double accuracy to ~1 ulp).
-__device__ __forceinline__ double rsqrt_nr(double a) {
-  double y = __builtin_amdgcn_rsq(a);
-  y = y * fma(-0.5 * a * y, y, 1.5);
-  y = y * fma(-0.5 * a * y, y, 1.5);
-  return y;
-}
-
-// Hand-off point between lanes of one wave through LDS.  LDS instructions of a wave execute
-// in issue order, so no hardware wait is needed; what must not happen is the COMPILER moving
-// a load that reads another lane's data above the store that wrote it (from one lane's
-// point of view the two addresses differ, so a single-thread fence does not forbid it).  A
-// wavefront-scope fence is the construct that orders memory accesses across the lanes of
-// the wave; it emits no instruction.
-__device__ __forceinline__ void lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// x[i] as a select chain over register values.  The empty asm makes each element an opaque
-// register value: without it InstCombine turns the select of array loads into a load from a
-// selected address, which keeps the whole parameter array in scratch memory (reloaded in
-// every MH step of the 2-chains-per-SIMD build).
-__device__ __forceinline__ double pget(const double (&x)[4], int i) {
-  double a = x[0], b = x[1], c = x[2], d = x[3];
-  asm("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-  return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d));
-}
-// the general-white-noise instances (GEN): up to 8 parameters
-__device__ __forceinline__ double pget(const double (&x)[8], int i) {
-  double v[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    v[k] = x[k];
-    asm("" : "+v"(v[k]));
-  }
-  double r = v[7];
-#pragma unroll
-  for (int k = 6; k >= 0; --k) r = (i == k) ? v[k] : r;
-  return r;
-}
-__device__ __forceinline__ int iget4(const int* a, int i) {   // a[i], i < 4
-  return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3]));
-}
-template <int N>
-__device__ __forceinline__ int iget(const int* a, int i) {   // a[i], i < N (4 or 8)
-  if constexpr (N == 4) {
-    return iget4(a, i);
-  } else {
-    int r = a[N - 1];
-#pragma unroll
-    for (int k = N - 2; k >= 0; --k) r = (i == k) ? a[k] : r;
-    return r;
-  }
-}
-
-// The jump (xi * sigma) * scale exactly as numpy evaluates it (gibbs.py:97,130): no FMA
-// contraction, so x + jump matches the reference bit for bit.
-__device__ __forceinline__ double mh_step(double xi, double sig, double scale) {
-#pragma clang fp contract(off)
-  return (xi * sig) * scale;
-}
-
-// numpy legacy binomial(1, p) given its uniform (inversion branch, random_binomial).
-__device__ __forceinline__ int bern_legacy(double p, double u) {
-  if (p == 0.0) return 0;
-  if (p <= 0.5) return u > exp(log(1.0 - p)) ? 1 : 0;
-  const double qq = 1.0 - p;
-  return u > exp(log(1.0 - qq)) ? 0 : 1;
-}
-
-// cos(2 pi u) for u in [0, 1): folded to a quarter turn, then the Taylor series of cos or
-// sin on [0, pi/4] (truncation < 1e-16), chosen by select.  Lighter than OCML's cospi
-// (fewer live registers inside the per-TOA gamma loops).
-__device__ __forceinline__ double cos2pi(double u) {
-  double x = u < 0.5 ? u : 1.0 - u;            // cos(2 pi (1 - u)) = cos(2 pi u)
-  const double sg = x > 0.25 ? -1.0 : 1.0;     // cos(2 pi (1/2 - x)) = -cos(2 pi x)
-  x = x > 0.25 ? 0.5 - x : x;                  // x in [0, 1/4]
-  const bool sn = x > 0.125;                   // cos(2 pi x) = sin(2 pi (1/4 - x))
-  const double t = (sn ? 0.25 - x : x) * 6.283185307179586477;   // t in [0, pi/4]
-  const double t2 = t * t;
-  double c = 1.0 / 20922789888000.0;           // 1/16!
-  c = fma(c, t2, -1.0 / 87178291200.0);
-  c = fma(c, t2, 1.0 / 479001600.0);
-  c = fma(c, t2, -1.0 / 3628800.0);
-  c = fma(c, t2, 1.0 / 40320.0);
-  c = fma(c, t2, -1.0 / 720.0);
-  c = fma(c, t2, 1.0 / 24.0);
-  c = fma(c, t2, -0.5);
-  c = fma(c, t2, 1.0);
-  double sv = 1.0 / 355687428096000.0;         // 1/17!
-  sv = fma(sv, t2, -1.0 / 1307674368000.0);
-  sv = fma(sv, t2, 1.0 / 6227020800.0);
-  sv = fma(sv, t2, -1.0 / 39916800.0);
-  sv = fma(sv, t2, 1.0 / 362880.0);
-  sv = fma(sv, t2, -1.0 / 5040.0);
-  sv = fma(sv, t2, 1.0 / 120.0);
-  sv = fma(sv, t2, -1.0 / 6.0);
-  sv = fma(sv, t2, 1.0) * t;
-  return sg * (sn ? sv : c);
-}
-
-// sin(2 pi u) = cos(2 pi (u - 1/4)), the argument wrapped back into [0, 1)
-__device__ __forceinline__ double sin2pi(double u) {
-  return cos2pi(u < 0.25 ? u + 0.75 : u - 0.25);
-}
-
-// Box-Muller normal from one Philox draw (its cosine half).
-__device__ __forceinline__ double normal_from(const Rng& rng, uint32_t index, uint32_t tag) {
-  double a, b;
-  rng.uniform2(index, tag, a, b);
-  return sqrt(-2.0 * log(1.0 - a)) * cos2pi(b);
-}
-
-// Both Box-Muller normals of one Philox draw: normals 2k and 2k + 1 of a stream.
-__device__ __forceinline__ void normal_pair(const Rng& rng, uint32_t k, uint32_t tag,
-                                            double& n0, double& n1) {
-  double a, b;
-  rng.uniform2(k, tag, a, b);
-  const double r = sqrt(-2.0 * log(1.0 - a));
-  n0 = r * cos2pi(b);
-  n1 = r * sin2pi(b);
-}
-
-// Normal j of a stream (one element of normal_pair(j / 2)).
-__device__ __forceinline__ double normal_k(const Rng& rng, uint32_t j, uint32_t tag) {
-  double n0, n1;
-  normal_pair(rng, j >> 1, tag, n0, n1);
-  return (j & 1u) ? n1 : n0;
-}
-
-// Marsaglia-Tsang Gamma(a, 1); a < 1 via the a+1 boost.  Attempts go in pairs: one Philox
-// draw gives both Box-Muller normals, a second the two acceptance uniforms.  Bounded.
-__device__ double gamma_mt(double a, const Rng& rng, uint32_t index, uint32_t tag) {
-  double boost = 1.0;
-  if (a < 1.0) {
-    double ub, unused;
-    rng.uniform2(index, tag | 0xFFFFFFu, ub, unused);
-    boost = exp(log(1.0 - ub) / a);
-    a += 1.0;
-  }
-  const double d = a - 1.0 / 3.0;
-  const double cc = 1.0 / sqrt(9.0 * d);
-#pragma unroll 1
-  for (uint32_t att = 0; att < 128u; ++att) {
-    double u1, u2, ua, ub;
-    rng.uniform2(index, tag | (2u * att), u1, u2);
-    rng.uniform2(index, tag | (2u * att + 1u), ua, ub);
-    const double r = sqrt(-2.0 * log(1.0 - u1));
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const double xn = r * (h == 0 ? cos2pi(u2) : sin2pi(u2));
-      const double u3 = h == 0 ? ua : ub;
-      double v = 1.0 + cc * xn;
-      if (v <= 0.0) continue;
-      v = v * v * v;
-      const double x2 = xn * xn;
-      if (u3 < 1.0 - 0.0331 * x2 * x2) return d * v * boost;
-      if (log(u3) < 0.5 * x2 + d * (1.0 - v + log(v))) return d * v * boost;
-    }
-  }
-  return d * boost;
-}
-
-// gamma_mt for NS draws at once -- draw s with shape a[s] and Philox index index0 + 64 s,
-// for the slots in `active` -- in one rejection loop, so the independent draws' dependency
-// chains interleave.  Every draw consumes exactly gamma_mt's variates in gamma_mt's order,
-// hence returns bitwise gamma_mt(a[s], rng, index0 + 64 s, tag).
-template <int NS>
-__device__ __forceinline__ void gamma_mt_slots(const double (&a)[NS], unsigned active,
-                                               const Rng& rng, uint32_t index0, uint32_t tag,
-                                               double (&out)[NS]) {
-  double d[NS], cc[NS], boost[NS];
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    double as = a[s];
-    boost[s] = 1.0;
-    if (((active >> s) & 1u) && as < 1.0) {
-      double ub, unused;
-      rng.uniform2(index0 + 64u * s, tag | 0xFFFFFFu, ub, unused);
-      boost[s] = exp(log(1.0 - ub) / as);
-      as += 1.0;
-    }
-    d[s] = as - 1.0 / 3.0;
-    cc[s] = 1.0 / sqrt(9.0 * d[s]);
-    out[s] = d[s] * boost[s];                 // gamma_mt's value after 256 failed attempts
-  }
-  unsigned pend = active;
-#pragma unroll 1
-  for (uint32_t att = 0; att < 128u && pend; ++att) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (!((pend >> s) & 1u)) continue;
-      double u1, u2, ua, ub;
-      rng.uniform2(index0 + 64u * s, tag | (2u * att), u1, u2);
-      rng.uniform2(index0 + 64u * s, tag | (2u * att + 1u), ua, ub);
-      const double r = sqrt(-2.0 * log(1.0 - u1));
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (!((pend >> s) & 1u)) break;
-        const double xn = r * (h == 0 ? cos2pi(u2) : sin2pi(u2));
-        const double u3 = h == 0 ? ua : ub;
-        double v = 1.0 + cc[s] * xn;
-        if (v <= 0.0) continue;
-        v = v * v * v;
-        const double x2 = xn * xn;
-        if (u3 < 1.0 - 0.0331 * x2 * x2 || log(u3) < 0.5 * x2 + d[s] * (1.0 - v + log(v))) {
-          out[s] = d[s] * v * boost[s];
-          pend &= ~(1u << s);
-        }
-      }
-    }
-  }
-}
-
-// Right-looking LDL^T-scaled Cholesky on the cyclic register layout.
-//
-// Registers keep RAW columns: after column k is eliminated, slot values hold
-// a_ik = L_ik * sqrt(a_kk) (the a_kk are the pivots), so L_ik = a_ik / sqrt(a_kk) is never
-// formed inside the factorisation; the rank-1 update is a_ij -= (a_ik / a_kk) * a_jk.
-// After each step every lane publishes its slot column that holds the next column into
-// its own LDS column buffer colq[q][.] (no owner test, no selects); step k reads the
-// buffer of q = k % 8.  Rows <= k are masked on the reading side (only slot K can hold
-// them).  The slot column holding column k+1 is updated first so its publication (the
-// step-to-step dependency through LDS) is issued before the rest of the trailing update.
-// Outputs per column: the pivot a_kk and the augmented-row entry a_{raug,k}.  Nothing is
-// captured per step (the step is VALU-issue-bound): an eliminated column is frozen in the
-// registers (the column-side mask zeroes every later update to it), so chol_harvest reads
-// both from L after the elimination; chol_stats then gives sum log a_kk (= log|Sigma| over
-// these columns, as mantissa product + exponent sum), sum a_{raug,k}^2 / a_kk (= the
-// d^T Sigma^-1 d contribution) and the failure flag.
-struct CholCtx {
-  double* colq;   // [8][MT] the published column (paired tail: the even column, [8][PW])
-  double* junk;   // [8][MT] where the other lanes' publishing stores land (see chol_publish)
-  double* colq2;  // [8][MT - KP] paired tail: the odd column (rows >= KP)
-  int lane, p, q, raug;
-  double mant, quad;
-  int expo, fail;
-  // pivots a_kk and augmented-row entries a_{raug,k}: column k kept by lane k % 64 in
-  // slot k / 64 (filled by chol_harvest)
-  double apr[2], zr[2];
-};
-
-// Publish column 8s + QQ: its owner lanes (q == QQ) write their slot column s, rows >= s.
-// Every lane stores ("pad, don't mask"): the others' stores go to the junk rows, so the
-// elimination stays free of lane-divergent control flow, which at this register pressure
-// makes the allocator spill kilobytes per lane.
-// The published column carries zeros in its rows <= its own index (slot row s, p <= QQ: the
-// frozen rows and the pivot row), so the readers' row- and column-side multipliers come out
-// masked without a select of their own (one select here instead of two per reader side).
-template <int MT, int QQ>
-__device__ __forceinline__ void chol_publish(const double (&L)[SL(MT, 0)], CholCtx& cc, int s) {
-  double* dst = (cc.q == QQ ? cc.colq : cc.junk) + MT * cc.p;
-  const bool live = cc.p > QQ;
-#pragma unroll
-  for (int r2 = 0; r2 < MT; r2 += 2) {          // rows (r2, r2+1)
-    if (r2 >= s) {  // one ds_write_b128 per row pair (16-byte aligned: MT, r2 even)
-      typedef double v2_t __attribute__((ext_vector_type(2)));
-      const double v0 = (r2 == s) ? (live ? L[SL(r2, s)] : 0.0) : L[SL(r2, s)];
-      *(v2_t*)(dst + r2) = (v2_t){v0, L[SL(r2 + 1, s)]};
-    } else if (r2 + 1 >= s)
-      dst[r2 + 1] = live ? L[SL(r2 + 1, s)] : 0.0;
-  }
-}
-
-// 1/a: hardware estimate (~2^-24) + one Newton step (~2e-15 relative, measured on
-// MI355X by tools/ubench/rcp_acc.hip); on every column step's critical path.
-__device__ __forceinline__ double rcp_nr1(double a) {
-  const double y = __builtin_amdgcn_rcp(a);
-  return fma(y, fma(-a, y, 1.0), y);
-}
-
-// Per-thread sum of logs as a running product: mantissa product + exponent sum (v_frexp),
-// one log per thread at the end instead of one per TOA (the per-TOA log dominated the white
-// block's 21 likelihood rescans; both paths).  The mantissa product is renormalised every 128 factors
-// (each factor >= 1/2, so it stays far above the fp64 underflow threshold).
-struct LogProd {
-  double mp = 1.0;
-  int ex = 0, k = 0;
-  __device__ __forceinline__ void mul(double v) {
-    int e;
-    mp *= frexp(v, &e);
-    ex += e;
-    if ((++k & 127) == 0) {
-      mp = frexp(mp, &e);
-      ex += e;
-    }
-  }
-  __device__ __forceinline__ double log_sum() const {
-    return log(mp) + (double)ex * 0.693147180559945309417;
-  }
-};
-
-// a / b for positive normal operands without the IEEE division sequence (v_div_scale /
-// v_div_fmas / v_div_fixup): reciprocal estimate, one Newton step, then one residual
-// correction of the quotient (within 1 ulp of the rounded quotient).
-__device__ __forceinline__ double div_pos(double a, double b) {
-  const double y = rcp_nr1(b);
-  const double q0 = a * y;
-  return fma(fma(-b, q0, a), y, q0);
-}
-
-// Raw column k as seen by this lane: rows 8r+p (lr), rows 8r+q (lc), the augmented row
-// entry, the pivot and its reciprocal.
-template <int MT>
-struct ColView {
-  double lr[MT], lc[MT];
-  double akk;
-  double y0, e;  // rcp estimate of 1/a_kk and its Newton residual 1 - a_kk y0
-};
-
-// 1/a_kk in two halves: the estimate and residual start the step's two dependent chains
-// (the critical factor below and the trailing-update reciprocal y0 + y0 e).
-template <int MT>
-__device__ __forceinline__ void pivot_rcp(ColView<MT>& c) {
-  c.y0 = __builtin_amdgcn_rcp(c.akk);
-  c.e = fma(-c.akk, c.y0, 1.0);
-}
-
-// Rows >= K of a published column [8][STRIDE] whose first stored row is R0 (the one-column
-// steps: colq, stride MT, R0 = 0; the paired tail: colq / colq2, stride MT - KP, R0 = KP).
-template <int MT, int K, int STRIDE = MT, int R0 = 0>
-__device__ __forceinline__ void chol_load(const double* buf, const CholCtx& cc, ColView<MT>& c) {
-  static_assert(MT % 2 == 0 && STRIDE % 2 == 0 && R0 % 2 == 0 && K >= R0,
-                "128-bit column loads need 16-byte alignment");
-  const double* cr = buf + STRIDE * cc.p - R0;
-  const double* cq = buf + STRIDE * cc.q - R0;
-#pragma unroll
-  for (int r2 = 0; r2 < MT; r2 += 2) {          // rows (r2, r2+1)
-    if (r2 >= K) {  // 128-bit loads (16-byte aligned: MT, r2 even)
-      typedef double v2_t __attribute__((ext_vector_type(2)));
-      const v2_t a = *(const v2_t*)(cr + r2);
-      const v2_t b = *(const v2_t*)(cq + r2);
-      c.lr[r2] = a[0];
-      c.lr[r2 + 1] = a[1];
-      c.lc[r2] = b[0];
-      c.lc[r2 + 1] = b[1];
-    } else if (r2 + 1 >= K) {
-      c.lr[r2 + 1] = cr[r2 + 1];
-      c.lc[r2 + 1] = cq[r2 + 1];
-    }
-  }
-}
-
-// ---- Paired tail: two columns per LDS hand-off ------------------------------------------
-// From slot column KP on, columns k and k+1 (k even, both in slot column KB) are
-// published together, column k+1 still RAW with respect to column k.  Every lane applies
-// column k's update to its own copy of column k+1 (one FMA per loaded row, the multiplier
-// tk = a(k+1,k) / a_kk a wave-uniform scalar from the owner lanes' registers), so a hand-off
-// serves two columns: the tail of the elimination is latency-bound on the ~140-cycle
-// write -> read hand-off, and this halves the number of hand-offs.
-// Every matrix element still receives the one-column steps' FMAs, with the same operands, in
-// the same order (including which slot column takes the column-scaled form), and the
-// corrected copy of column k+1 is the expression its owner lanes evaluate in the one-column
-// step: the factor is bitwise that of chol_step alone.
-template <int MT, int QQ, int KP>
-__device__ __forceinline__ void chol_publish_pair(const double (&L)[SL(MT, 0)], CholCtx& cc,
-                                                  int s) {
-  constexpr int PW = MT - KP;
-  const bool even = cc.q == QQ, odd = cc.q == QQ + 1;
-  double* dst = (even ? cc.colq : (odd ? cc.colq2 : cc.junk)) + PW * cc.p - KP;
-  const bool live = cc.p > (odd ? QQ + 1 : QQ);   // zero rows <= the column's own index
-#pragma unroll
-  for (int r2 = KP; r2 < MT; r2 += 2) {
-    if (r2 >= s) {
-      typedef double v2_t __attribute__((ext_vector_type(2)));
-      const double v0 = (r2 == s) ? (live ? L[SL(r2, s)] : 0.0) : L[SL(r2, s)];
-      *(v2_t*)(dst + r2) = (v2_t){v0, L[SL(r2 + 1, s)]};
-    } else if (r2 + 1 >= s)
-      dst[r2 + 1] = live ? L[SL(r2 + 1, s)] : 0.0;
-  }
-}
-
-// Publish columns 8KB + QQ and 8KB + QQ + 1 (slot column KB already updated by every earlier
-// column), load both, and turn the odd one into its value after the even column's update.
-// Returns nothing; n0 / n1 are ready for chol_pair (pivots and reciprocals set).
-template <int MT, int KB, int QQ, int KP>
-__device__ __forceinline__ void pair_handoff(double (&L)[SL(MT, 0)], CholCtx& cc,
-                                             ColView<MT>& n0, ColView<MT>& n1) {
-  constexpr int PW = MT - KP;
-  static_assert(QQ % 2 == 0 && KB >= KP && KP % 2 == 0 && KP >= KP_MIN,
-                "pairs start at even columns of the paired tail");
-  lds_order();                       // the previous pair's loads precede the overwrite
-  chol_publish_pair<MT, QQ, KP>(L, cc, KB);
-  const double a22 = rdlane(L[SL(KB, KB)], 9 * QQ);       // a(k, k)
-  const double a32 = rdlane(L[SL(KB, KB)], 9 * QQ + 8);   // a(k+1, k)
-  const double a33 = rdlane(L[SL(KB, KB)], 9 * QQ + 9);   // a(k+1, k+1), before column k
-  lds_order();
-  ColView<MT> raw;
-  chol_load<MT, KB, PW, KP>(cc.colq, cc, n0);
-  chol_load<MT, KB, PW, KP>(cc.colq2, cc, raw);
-  n0.akk = a22;
-  pivot_rcp<MT>(n0);
-  // the one-column step's factor of column k+1's owner lanes (lc[K1] y0 refined)
-  const double t = a32 * n0.y0;
-  const double tk = fma(t, n0.e, t);
-  n1.akk = fma(-a32, tk, a33);
-  pivot_rcp<MT>(n1);
-#pragma unroll
-  for (int r = KB; r < MT; ++r) {
-    n1.lr[r] = fma(-n0.lr[r], tk, raw.lr[r]);
-    n1.lc[r] = fma(-n0.lc[r], tk, raw.lc[r]);
-  }
-  // rows <= k+1 of slot KB: frozen / pivot rows of column k+1, as its publication would carry
-  n1.lr[KB] = (cc.p > QQ + 1) ? n1.lr[KB] : 0.0;
-  n1.lc[KB] = (cc.q > QQ + 1) ? n1.lc[KB] : 0.0;
-}
-
-// Columns k = 8K + KK and k+1 (KK even); c0 / c1 as pair_handoff leaves them.
-template <int MT, int K, int KK, int KEND, int KP>
-__device__ __forceinline__ void chol_pair(double (&L)[SL(MT, 0)], CholCtx& cc, ColView<MT>& c0,
-                                          ColView<MT>& c1) {
-  static_assert(KK % 2 == 0, "pairs start at even columns");
-  constexpr int k = 8 * K + KK;
-  constexpr int KB = (KK == 6) ? K + 1 : K;   // slot column of columns k+2, k+3
-  constexpr int QB = (KK + 2) & 7;
-  constexpr bool NEXT = k + 2 < KEND;
-  static_assert(k + 2 <= KEND, "the paired tail covers an even number of columns");
-  // column k's column-scaled factor (its "critical" slot column is K, which holds k+1)
-  const double t0 = c0.lc[K] * c0.y0;
-  const double tk0 = fma(t0, c0.e, t0);
-  const double sk0 = fma(c0.y0, c0.e, c0.y0);
-  // column k+1's (its critical slot column is KB, which holds k+2)
-  const double t1 = c1.lc[KB < MT ? KB : K] * c1.y0;
-  const double tk1 = fma(t1, c1.e, t1);
-  const double sk1 = fma(c1.y0, c1.e, c1.y0);
-  ColView<MT> n0, n1;
-  if constexpr (KB < MT) {
-    // critical path: slot column KB (columns k+2, k+3) by column k, then by column k+1
-#pragma unroll
-    for (int r = KB; r < MT; ++r) {
-      double v = L[SL(r, KB)];
-      if constexpr (KB == K)
-        v = fma(-c0.lr[r], tk0, v);
-      else
-        v = fma(-(c0.lr[r] * sk0), c0.lc[KB], v);
-      L[SL(r, KB)] = fma(-c1.lr[r], tk1, v);
-    }
-    if constexpr (NEXT) pair_handoff<MT, KB, QB, KP>(L, cc, n0, n1);
-  }
-  // the rest of the two columns' trailing update (row-scaled, as the one-column steps)
-  double lrs0[MT], lrs1[MT];
-#pragma unroll
-  for (int r = K; r < MT; ++r) {
-    lrs0[r] = c0.lr[r] * sk0;
-    lrs1[r] = c1.lr[r] * sk1;
-  }
-#pragma unroll
-  for (int s = K; s < MT; ++s) {
-    if (s == KB) continue;
-#pragma unroll
-    for (int r = s; r < MT; ++r) {
-      if (s == K) {
-        // KK == 6: slot column K is column k's critical one (it holds k+1); column k+1 (the
-        // slot's last) leaves it alone
-        L[SL(r, s)] = fma(-c0.lr[r], tk0, L[SL(r, s)]);
-      } else {
-        const double v = fma(-lrs0[r], c0.lc[s], L[SL(r, s)]);
-        L[SL(r, s)] = fma(-lrs1[r], c1.lc[s], v);
-      }
-    }
-  }
-  if constexpr (NEXT) chol_pair<MT, KB, QB, KEND, KP>(L, cc, n0, n1);
-}
-
-// Step k = 8K + KK, software-pipelined: the slot column holding column k+1 is updated
-// and published first, column k+1's loads and pivot reciprocal are issued, and only then
-// does the rest of step k's trailing update run (covering their latency).
-template <int MT, int K, int KK, int KEND, int KP>
-__device__ __forceinline__ void chol_step(double (&L)[SL(MT, 0)], CholCtx& cc,
-                                          ColView<MT>& cur) {
-  constexpr int k = 8 * K + KK;
-  constexpr int K1 = (KK == 7) ? K + 1 : K;  // slot column of column k+1
-  constexpr int KK1 = (KK + 1) & 7;
-  constexpr bool NEXT = k + 1 < KEND;
-  // rows <= k of slot K arrive as zeros (chol_publish): frozen entries stay untouched
-  // column k+1 starts the paired tail: publish it together with k+2 (pair_handoff)
-  constexpr bool TOPAIR = NEXT && K1 >= KP;
-  static_assert(!TOPAIR || KK1 == 0, "the paired tail starts at a slot column");
-  ColView<MT> nxt, nxt2;
-  if constexpr (K1 < MT) {
-    // critical path: slot column K1 (holds column k+1).  Its factor a_{8K1+q,k} / a_kk is
-    // one value per lane (lc y0 refined by the Newton term), so the published column
-    // feeds this FMA directly: LDS load -> FMA and rcp -> mul -> FMA -> FMA are the two
-    // step-to-step chains (the row-scaled lrs below stay off them).
-    const double t0 = cur.lc[K1] * cur.y0;
-    const double tk = fma(t0, cur.e, t0);
-#pragma unroll
-    for (int r = K1; r < MT; ++r) L[SL(r, K1)] = fma(-cur.lr[r], tk, L[SL(r, K1)]);
-    if constexpr (TOPAIR) {
-      pair_handoff<MT, K1, 0, KP>(L, cc, nxt, nxt2);
-    } else if constexpr (NEXT) {
-      lds_order();                   // column k's loads precede its overwrite
-      chol_publish<MT, KK1>(L, cc, K1);
-      nxt.akk = rdlane(L[SL(K1, K1)], 9 * KK1);
-      lds_order();
-      chol_load<MT, K1>(cc.colq, cc, nxt);
-      pivot_rcp<MT>(nxt);
-    }
-  }
-  // lrs = a_ik / a_kk for the rest of the trailing update (one multiply per row, then one
-  // FMA per element)
-  const double sk = fma(cur.y0, cur.e, cur.y0);
-  double lrs[MT];
-#pragma unroll
-  for (int r = K; r < MT; ++r) lrs[r] = cur.lr[r] * sk;
-  // off the critical path: the rest of the trailing update
-#pragma unroll
-  for (int s = K; s < MT; ++s) {
-    if (s == K1 || (KK == 7 && s == K)) continue;  // slot column K is done when KK == 7
-#pragma unroll
-    for (int r = s; r < MT; ++r) L[SL(r, s)] = fma(-lrs[r], cur.lc[s], L[SL(r, s)]);
-  }
-  if constexpr (TOPAIR)
-    chol_pair<MT, K1, 0, KEND, KP>(L, cc, nxt, nxt2);
-  else if constexpr (NEXT)
-    chol_step<MT, K1, KK1, KEND, KP>(L, cc, nxt);
-}
-
-// Eliminate columns [8*KLO, KEND) (compile-time: no branch between steps), updating the
-// trailing slots.
-template <int MT, int KLO, int KEND, int KP>
-__device__ __forceinline__ void chol_range(double (&L)[SL(MT, 0)], CholCtx& cc) {
-  static_assert(KEND > 8 * KLO && KEND <= 8 * MT, "bad elimination range");
-  if constexpr (KLO >= KP) {
-    ColView<MT> c0, c1;
-    pair_handoff<MT, KLO, 0, KP>(L, cc, c0, c1);
-    chol_pair<MT, KLO, 0, KEND, KP>(L, cc, c0, c1);
-  } else {
-    chol_publish<MT, 0>(L, cc, KLO);
-    ColView<MT> c;
-    c.akk = rdlane(L[SL(KLO, KLO)], 0);
-    lds_order();
-    chol_load<MT, KLO>(cc.colq, cc, c);
-    pivot_rcp<MT>(c);
-    chol_step<MT, KLO, 0, KEND, KP>(L, cc, c);
-  }
-  lds_order();
-}
-
-// The same elimination without the next column's prefetch (one ColView live instead of
-// two): used for the timing-model columns, where every slot of L is still live and the
-// register budget of two chains per SIMD has no room for the double buffer.
-template <int MT, int K, int KK, int KEND>
-__device__ __forceinline__ void chol_step_lean(double (&L)[SL(MT, 0)], CholCtx& cc) {
-  constexpr int k = 8 * K + KK;
-  constexpr int K1 = (KK == 7) ? K + 1 : K;
-  constexpr int KK1 = (KK + 1) & 7;
-  ColView<MT> cur;
-  lds_order();                       // the previous step's loads precede this publication
-  chol_publish<MT, KK>(L, cc, K);
-  cur.akk = rdlane(L[SL(K, K)], 9 * KK);
-  lds_order();
-  chol_load<MT, K>(cc.colq, cc, cur);
-  pivot_rcp<MT>(cur);
-  // rows <= k of slot K arrive as zeros (chol_publish): frozen entries stay untouched
-  const double sk = fma(cur.y0, cur.e, cur.y0);
-#pragma unroll
-  for (int s = K; s < MT; ++s) {
-    if (KK == 7 && s == K) continue;   // slot column K is complete
-#pragma unroll
-    for (int r = s; r < MT; ++r) L[SL(r, s)] = fma(-(cur.lr[r] * sk), cur.lc[s], L[SL(r, s)]);
-  }
-  if constexpr (k + 1 < KEND) chol_step_lean<MT, K1, KK1, KEND>(L, cc);
-}
-
-template <int MT, int KLO, int KEND>
-__device__ __forceinline__ void chol_range_lean(double (&L)[SL(MT, 0)], CholCtx& cc) {
-  static_assert(KEND > 8 * KLO && KEND <= 8 * MT, "bad elimination range");
-  chol_step_lean<MT, KLO, 0, KEND>(L, cc);
-  lds_order();
-}
-
-// Lane-parallel statistics of an elimination over columns [KLO, KEND) from the per-lane
-// pivots / aug entries (lane k % 64 of apr[k / 64], zr[k / 64]): prod a_kk as mantissa
-// product + exponent sum (log taken once by the caller), sum a_{raug,k}^2 / a_kk and the
-// failure flag, all wave-uniform.  Branch-free on purpose: a lane-divergent region here,
-// inside the register-critical hyper block, makes the allocator spill ~1.4 KB per lane.
-__device__ __forceinline__ double bperm(double v, int src_lane) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_ds_bpermute(4 * src_lane, (int)(b & 0xffffffffll));
-  const int hi = __builtin_amdgcn_ds_bpermute(4 * src_lane, (int)(b >> 32));
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// After an elimination over columns [KLO, KEND): the pivot of column j = 8K+q is frozen in
-// lane (q,q) slot (K,K) and its augmented-row entry in lane (RA%8, q) slot (RA/8, K); lane
-// j % 64 of apr / zr[j / 64] fetches both (one lane permute per slot column, no branch).
-template <int MT, int KLO, int KEND, int RA>
-__device__ __forceinline__ void chol_harvest(const double (&L)[SL(MT, 0)], CholCtx& cc) {
-  constexpr int R = RA / 8, PA = RA % 8;
-  static_assert(KEND <= RA && RA < 8 * MT, "augmented row below the eliminated columns");
-#pragma unroll
-  for (int K = KLO / 8; K <= (KEND - 1) / 8; ++K) {
-    const double vd = bperm(L[SL(K, K)], 9 * cc.q);
-    const double vz = bperm(L[SL(R, K)], 8 * PA + cc.q);
-    const int j = 8 * K + cc.q;
-    const bool in = (j >= KLO) && (j < KEND);
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-      const bool mine = in && (8 * sl + cc.p == K);
-      cc.apr[sl] = mine ? vd : cc.apr[sl];
-      cc.zr[sl] = mine ? vz : cc.zr[sl];
-    }
-  }
-}
-
-template <int KLO, int KEND>
-__device__ __forceinline__ void chol_stats(CholCtx& cc) {
-  double mm = 1.0, qd = 0.0;
-  int ee = 0, f = 0;
-#pragma unroll
-  for (int sl = 0; sl < 2; ++sl) {
-    const int j = 64 * sl + cc.lane;
-    const bool in = (j >= KLO) && (j < KEND);
-    const double a = in ? cc.apr[sl] : 1.0, z = in ? cc.zr[sl] : 0.0;
-    f |= !(a > 0.0) ? 1 : 0;
-    int e;
-    mm *= frexp(a, &e);
-    ee += e;
-    qd = fma(z * z, rcp_nr1(a), qd);
-  }
-  mm *= dpp<DPP_XOR1>(mm);
-  mm *= dpp<DPP_XOR2>(mm);
-  mm *= dpp<DPP_ROR4>(mm);
-  mm *= dpp<DPP_ROR8>(mm);
-  cc.mant = (rdlane(mm, 0) * rdlane(mm, 16)) * (rdlane(mm, 32) * rdlane(mm, 48));
-  cc.expo = wave_sum_i(ee);
-  cc.quad = wave_sum(qd);
-  cc.fail = __ballot(f) != 0ull ? 1 : 0;
-}
 
 // WPB = chains (waves) per workgroup (4 = one per SIMD; the host picks 2 or 1 when the
 // launch has fewer chains than CUs x 4, so the chains spread over every CU).  OCC = chains
@@ -1128,7 +296,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
   auto gen_n0 = [&](const double (&xq)[PX], double s2, int ie, int iq)
       __attribute__((always_inline)) -> double {
     const double ef = ie >= 0 ? pget(xq, ie) : md.efac_const;
-    return ef * ef * s2 + exp(2.0 * pget(xq, iq) * 2.302585092994045684);
+    return ef * ef * s2 + pow10_2(pget(xq, iq));
   };
   // N0 of noise class k (wave-uniform k)
   auto cls_n0 = [&](const double (&xq)[PX], int k) __attribute__((always_inline)) -> double {
@@ -1168,12 +336,12 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
   // Q = 10^(2 equad) is passed in: the MH steps carry it (Q_q = Q_x * 10^(2 delta)).
   auto lnl_white = [&](const double (&xq)[PX], double Q) __attribute__((always_inline)) -> double {
     const double ef2 = efac2_of(xq);
-    if (GEN && hncls == 1) {
-      const double N0 = cls_n0(xq, 0);
-      return -0.5 * ((wcls_la + md.ccount[0] * log(N0)) + rdlane(wcls, 0) / N0);
-    }
-    if (!GEN && hncls == 1) {  // uniform: no reduction
-      const double N0 = ef2 * md.csig2[0] + Q;
+    if (hncls == 1) {  // uniform: no reduction
+      double N0;
+      if constexpr (GEN)
+        N0 = cls_n0(xq, 0);
+      else
+        N0 = ef2 * md.csig2[0] + Q;
       return -0.5 * ((wcls_la + md.ccount[0] * log(N0)) + rdlane(wcls, 0) / N0);
     }
     double sl = 0.0, sq = 0.0;
@@ -1209,6 +377,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
   // MH variates of one sweep (30 steps: 20 white then 10 hyper), produced in parallel by
   // lanes 0..29: u_scale, parameter index, jump normal, log(u_accept) (gibbs.py:95-104,
   // 128-137).  Tape mode copies the reference's recorded values instead.
+  // (the large path draws the same numbers with gst_draws.h mh_variate)
   auto mh_variates = [&](const double* tp) __attribute__((always_inline)) {
     if (lane < NWHITE + NHYPER) {
       const bool white = lane < NWHITE;
@@ -1245,7 +414,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
       e[0] = par;
       e[1] = delta;
       e[2] = la;
-      e[3] = exp(2.0 * delta * 2.302585092994045684);
+      e[3] = exp(2.0 * delta * LN10);
     }
     lds_order();
   };
@@ -1281,7 +450,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
   // Gram: G = T_aug^T diag(1/N) T_aug on fp64 MFMA, then TM elimination -> S0.
   auto gram_and_tm = [&](const double (&xq)[PX]) __attribute__((always_inline)) {
     const double ef2 = efac2_of(xq);
-    const double Q = exp(2.0 * pget(xq, md.idx_equad) * 2.302585092994045684);
+    const double Q = pow10_2(pget(xq, md.idx_equad));
     double sr = 0.0;
     double wlane[NS];   // the lane's weights w_t = 1 / N_t (the low-rank Gram reads them by lane)
     LogProd lp;
@@ -1668,7 +837,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     const double lA = pget(xq, iA);
     const double g = pget(xq, ig);
     // log phi_k = 2 lA ln10 - log(12 pi^2) + (g-3) log fyr - g log f_k + log df_k
-    const double lc = 2.0 * lA * 2.302585092994045684 - hl12 + (g - 3.0) * hlfyr;
+    const double lc = powerlaw_lc(lA, g, hl12, hlfyr);
     // S0 first: its 36 LDS loads are in flight while phi^-1 is computed (exp)
 #pragma unroll
     for (int r = K0; r < MT; ++r)
@@ -1681,22 +850,22 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
       if (lane < RA - hntmp)
         phbuf[hntmp + lane] =
             f_live ? exp(-(lc - g * lfreq_l + ldf_l)) + fshift
-                   : (geci >= 0 ? exp(-2.0 * pget(xq, geci) * 2.302585092994045684) + fshift : 1.0);
+                   : (geci >= 0 ? exp(-2.0 * pget(xq, geci) * LN10) + fshift : 1.0);
     } else {
       // every lane takes the exp (it sat in an exec-masked region of its own; the dummy
       // columns' lanes drop the value)
-      const double e = exp(-(lc - g * lfreq_l + ldf_l));
-      if (lane < RA - hntmp) phbuf[hntmp + lane] = f_live ? e + fshift : 1.0;
+      const double e = phi_inv_fourier(lc, g, lfreq_l, ldf_l, fshift);
+      if (lane < RA - hntmp) phbuf[hntmp + lane] = f_live ? e : 1.0;
     }
     // phbuf doubles as the eliminations' junk rows: restore the one other entry read
     // below, the augmented row's (no prior on the residual column)
     if (lane == 63) phbuf[raug] = 0.0;
     // sum_k log phi_k in closed form (no reduction on the critical path)
-    double logdet_phi = ((double)hnf * lc - g * hslf + hsldf) + hldtm;
+    double logdet_phi = logdet_phi_fourier(hnf, lc, g, hslf, hsldf, hldtm);
     if constexpr (GEN) {
       for (int b = 0; b < md.nb; ++b)   // log 10^(2 ecorr_b) per ECORR column of backend b
         if (md.ec_count[b] > 0.0)
-          logdet_phi += md.ec_count[b] * (2.0 * pget(xq, md.ecorr_b[b]) * 2.302585092994045684);
+          logdet_phi += logdet_phi_ecorr(md.ec_count[b], pget(xq, md.ecorr_b[b]));
     }
     lds_order();
 #pragma unroll
@@ -1718,10 +887,8 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     failed = cc.fail | fail_tm;
     if (failed) return -INFINITY;
     // log|Sigma| = sum log a_kk (pivots of the LDL^T-scaled elimination)
-    const double ld_sigma = log(ld_tm_m * mant) + (double)(ld_tm_e + expo) * 0.693147180559945309417;
-    double ll = -0.5 * (logdetN + rNr);
-    ll += 0.5 * ((quad_tm + quad) - ld_sigma - logdet_phi);
-    return ll;
+    const double ld_sigma = log(ld_tm_m * mant) + (double)(ld_tm_e + expo) * LN2;
+    return marginal_ll(logdetN, rNr, quad_tm + quad, ld_sigma, logdet_phi);
   };
 
   // pair mode: both waves write the records (identical state): b and the TOA slots split
@@ -1861,7 +1028,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
         return -0.5 * ((sl + wcls_la) + sq);
       };
       const int ieq = md.idx_equad;
-      double Qx = exp(2.0 * pget(xv, ieq) * 2.302585092994045684);
+      double Qx = pow10_2(pget(xv, ieq));
       double l0 = lnl_lane(xv, Qx), p0 = lnprior(xv);
       // this lane's node: level j, path b
       const int node = lane + 1;
@@ -1940,7 +1107,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     } else if ((mask & 1u) || eval_only) {
       white_prep();
       double l0 = 0.0, p0 = 0.0;
-      double Qx = exp(2.0 * pget(xv, hieq) * 2.302585092994045684);
+      double Qx = pow10_2(pget(xv, hieq));
 #pragma unroll 1
       for (int step = -1; step < NWHITE; ++step) {
         if ((step & 3) == 0) fair_prio<OCC>(fair);
@@ -2377,7 +1544,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     GST_SUB_BEGIN
     // ---- outlier block: theta (gibbs.py:185-198)
     const double ef2 = efac2_of(xv);
-    const double Q = exp(2.0 * pget(xv, md.idx_equad) * 2.302585092994045684);
+    const double Q = pow10_2(pget(xv, md.idx_equad));
     const bool mix = (md.model == 2) || (md.model == 3);
     if ((mask & 8u) && mix) {
       int zs = 0;

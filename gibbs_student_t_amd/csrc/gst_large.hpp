@@ -26,12 +26,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "gst_kernel.hpp"
+#include "gst_chol.hpp"
+#include "gst_draws.h"
+#include "gst_model.h"
 #include "gst_plan.h"
+#include "gst_wave.hpp"
+#include "philox.hpp"
 
 namespace gst {
-
-constexpr double LN10 = 2.302585092994045684;
 
 struct LScratch {
   double* G;   // [C][mp*mp] Gram (row-major, lower triangle); kept for the floor pass
@@ -159,50 +161,6 @@ __device__ __forceinline__ void block_sum_k(double (&v)[K], double* red) {
   }
 }
 
-// MH variates of global step gs (0..19 white, 20..29 hyper) exactly as the persistent
-// kernel draws them (gst_kernel.hpp mh_variates): parameter, jump, log(u_acc), 10^(2 jump).
-__device__ __forceinline__ void mh_variate(const DevModel& md, const Rng& rng, const double* tp,
-                                           int gs, double* out4) {
-  const bool white = gs < NWHITE;
-  const int step = white ? gs : gs - NWHITE;
-  double us, par, xi, la;
-  if (tp) {
-    const double* e = tp + (white ? TP_WHITE : TP_HYPER) + 4 * step;
-    us = e[0];
-    par = e[1];
-    xi = e[2];
-    la = log(e[3]);
-  } else {
-    const uint32_t tag = white ? TAG_WHITE : TAG_HYPER;
-    double ua, ub, uidx, unused;
-    rng.uniform2(0u, tag | (uint32_t)(3 * step), ua, ub);
-    us = ua;
-    la = log(ub);
-    xi = normal_from(rng, 0u, tag | (uint32_t)(3 * step + 1));
-    const int nind = white ? md.nw : md.nh;
-    rng.uniform2(0u, tag | (uint32_t)(3 * step + 2), uidx, unused);
-    int k = (int)(uidx * nind);
-    k = k < nind - 1 ? k : nind - 1;
-    const int* ind = white ? md.wind : md.hind;
-    int pk = ind[0];
-#pragma unroll
-    for (int j = 1; j < PMAX; ++j) pk = (k == j) ? ind[j] : pk;
-    par = (double)pk;
-  }
-  int cnt = 0;
-#pragma unroll
-  for (int i = 0; i < 5; ++i) cnt += (md.mh_cdf[i] <= us) ? 1 : 0;
-  cnt = cnt < 4 ? cnt : 4;
-  const double scale = md.mh_size[0] * (cnt == 0) + md.mh_size[1] * (cnt == 1) +
-                       md.mh_size[2] * (cnt == 2) + md.mh_size[3] * (cnt == 3) +
-                       md.mh_size[4] * (cnt == 4);
-  const double delta = mh_step(xi, white ? md.sig_w : md.sig_h, scale);
-  out4[0] = par;
-  out4[1] = delta;
-  out4[2] = la;
-  out4[3] = exp(2.0 * delta * LN10);
-}
-
 typedef double XVec[PMAX];   // a chain's parameter vector (x, or an MH proposal)
 
 __device__ __forceinline__ double lnpriorP(const DevModel& md, const XVec& xq) {
@@ -274,7 +232,7 @@ __device__ __forceinline__ WhiteNoise white_noise(const DevModel& md, const XVec
       const double xe = xget(x, ei >= 0 ? ei : 0);
       const double ef = ei >= 0 ? xe : md.efac_const;
       w.ef2[b] = ef * ef;
-      w.Q[b] = exp(2.0 * xget(x, md.equad_b[b]) * LN10);
+      w.Q[b] = pow10_2(xget(x, md.equad_b[b]));
     } else {
       w.ef2[b] = 0.0;
       w.Q[b] = 0.0;
@@ -1199,6 +1157,8 @@ __device__ __forceinline__ HyperIn hyper_in(const DevModel& md, const LArgs& a, 
 // the prior side of the b-marginalised lnL (gibbs.py:288-329): log of the power law's
 // coefficient, log|phi| (its Fourier and timing-model part, then with the ECORR columns backend
 // by backend), phi^-1 of hyper column jc < nf + nec (+ f in the floor pass), and the sum
+// (hyper_lc .. hyper_ll: the twins of gst_draws.h powerlaw_lc, logdet_phi_fourier /
+// logdet_phi_ecorr, phi_inv_fourier / phi_inv_ecorr and marginal_ll -- change a law in both)
 __device__ __forceinline__ double hyper_lc(const DevModel& md, double lA, double g) {
   return 2.0 * lA * LN10 - md.log_12pi2 + (g - 3.0) * md.log_fyr;
 }
@@ -1489,6 +1449,9 @@ __global__ void __launch_bounds__(LBLK) lg_hyper(const DevModel* __restrict__ md
   auto lnl = [&](const XVec& q, int& failed) -> double {
     const double lA = xget(q, md.idx_logA);
     const double g = xget(q, md.idx_gamma);
+    // (written out: hyper_lc, phi_inv_col and hyper_logdet_phi, i.e. gst_draws.h's powerlaw_lc,
+    // phi_inv_fourier / phi_inv_ecorr and logdet_phi_fourier / logdet_phi_ecorr; this kernel's
+    // stage time follows where its code lands, so its text stays: DESIGN.md 4d.2a, 4d.2c)
     const double lc = 2.0 * lA * LN10 - md.log_12pi2 + (g - 3.0) * md.log_fyr;
     for (int f = tid; f < nf; f += LBLK) {
       if (f < nfr) {
@@ -1710,7 +1673,7 @@ __global__ void __launch_bounds__(LBLK) lg_hyper(const DevModel* __restrict__ md
     }
     failed = fl | fail_tm;
     if (failed) return -INFINITY;
-    double ll = -0.5 * (logdetN + rNr);
+    double ll = -0.5 * (logdetN + rNr);   // (marginal_ll, written out as the rest of this lnl)
     ll += 0.5 * ((quad_tm + quad) - (ld_tm + ld) - logdet_phi);
     return ll;
   };
@@ -2022,7 +1985,7 @@ __global__ void __launch_bounds__(64 * HR<MT>::WPB) lg_hyper_reg(const DevModel*
     }
     failed = cc.fail | in.fail_tm;
     if (failed) return -INFINITY;
-    const double ld = log(cc.mant) + (double)cc.expo * 0.693147180559945309417;
+    const double ld = log(cc.mant) + (double)cc.expo * LN2;   // (log_mant_exp, written out)
     return hyper_ll(in, in.quad_tm + cc.quad, in.ld_tm + ld, logdet_phi);
   };
 
@@ -2217,17 +2180,17 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
   auto lnl = [&](const XLds& xs, int& failed) __attribute__((always_inline)) -> double {
     const double g = xs.q[iG];
     const double lc = hyper_lc(md, xs.q[iA], g);
-    ph[lane] = (fl_ >= 0 && fl_ < nfr) ? exp(-(lc - g * lf_l + ldf_l)) + fsh : 0.0;
+    ph[lane] = (fl_ >= 0 && fl_ < nfr) ? phi_inv_fourier(lc, g, lf_l, ldf_l, fsh) : 0.0;
     double logdet_phi = hyper_logdet_phi0(md, lc, g);
     const double xb = pib >= 0 ? xs.q[pib] : 0.0;   // lane b: backend b's log10_ecorr
-    const double tb_ = ecc > 0.0 ? ecc * (2.0 * xb * LN10) : 0.0;
+    const double tb_ = ecc > 0.0 ? logdet_phi_ecorr(ecc, xb) : 0.0;
 #pragma unroll
     for (int b = 0; b < NBMAX; ++b)   // backend by backend, as lg_hyper<2>
       if (b < nb) logdet_phi += rdlane(tb_, b);
     const bool same = ecvalid && __ballot(pib >= 0 && xb != eck_l) == 0ull;
     CholCtx cc{colq, junk, colq2, lane, p, q, RA, 1.0, 0.0, 0, 0, {1.0, 1.0}, {0.0, 0.0}};
     if (!same) {
-      if (lane < NBMAX) phb[lane] = pib >= 0 ? exp(-2.0 * xb * LN10) + fsh : 0.0;
+      if (lane < NBMAX) phb[lane] = pib >= 0 ? phi_inv_ecorr(xb, fsh) : 0.0;
       eck_l = xb;
       // the epochs' coupling rows g_e (lane = X row), two groups of EG in flight
       const int rr = lane >> 3, pp = lane & 7;   // this lane's X row 8 rr + pp
@@ -2335,7 +2298,7 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
       chol_range<MT, 0, 16, H::KP>(L, cc);
       chol_harvest<MT, 0, 16, RA>(L, cc);
       chol_stats<0, 16>(cc);
-      tm_ld = log(cc.mant) + (double)cc.expo * 0.693147180559945309417;
+      tm_ld = log_mant_exp(cc.mant, cc.expo);
       tm_quad = cc.quad;
       tm_fail = cc.fail;
       tm_apr = cc.apr[0];
@@ -2362,7 +2325,7 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
     f_zr = cc.zr[0];
     failed = (cc.fail | tm_fail | fle) != 0;
     if (failed) return -INFINITY;
-    const double ld = log(cc.mant) + (double)cc.expo * 0.693147180559945309417;
+    const double ld = log_mant_exp(cc.mant, cc.expo);
     return hyper_ll(in, tm_quad + qde + cc.quad, tm_ld + lde + ld, logdet_phi);
   };
 

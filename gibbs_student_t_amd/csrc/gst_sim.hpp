@@ -18,7 +18,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "gst_kernel.hpp"
+#include "gst_draws.h"
+#include "gst_wave.hpp"
 #include "philox.hpp"
 
 namespace gst {
@@ -79,7 +80,7 @@ __global__ void __launch_bounds__(SIM_BLOCK) gst_simulate_kernel(SimArgs a) {
   // red-noise coefficients sqrt(phi_k) xi_k (log phi_k as the sampler's prior, model.powerlaw)
   if (!a.red) {
     const double lA = a.log10_A[d], g = a.gamma[d];
-    const double lc = 2.0 * lA * 2.302585092994045684 - a.log_12pi2 + (g - 3.0) * a.log_fyr;
+    const double lc = powerlaw_lc(lA, g, a.log_12pi2, a.log_fyr);
     for (int k = tid; k < a.nf; k += SIM_BLOCK)
       coef[k] = sqrt(exp(lc - g * a.lf[k] + a.ldf[k])) * normal_from(rng, (uint32_t)k, TAG_SIM_RED);
   }

@@ -4,7 +4,7 @@ The kernels draw every variate as a pure function of (seed, chain, sweep, tag, i
 (csrc/philox.hpp): Philox4x32-10 on the counter (index, tag, sweep, chain) with the key
 (seed low word, seed high word); one draw gives two 53-bit uniforms, (words 0, 1) and (words
 2, 3).  This module restates that layout and the maps the Metropolis blocks build on it
-(csrc/gst_kernel.hpp mh_variates, csrc/gst_large.hpp mh_variate), vectorised over any
+(csrc/gst_kernel.hpp mh_variates, csrc/gst_draws.h mh_variate), vectorised over any
 broadcastable chain / sweep / index arrays, so a test can write the tape a Philox-mode launch
 must be equivalent to.
 """
@@ -53,7 +53,7 @@ def uniform2(seed, chain, sweep, tag, index=0):
 
 
 def normal_from_uniforms(a, b):
-    """The cosine half of Box-Muller (gst_kernel.hpp normal_from)."""
+    """The cosine half of Box-Muller (gst_draws.h normal_from)."""
     return np.sqrt(-2.0 * np.log1p(-a)) * np.cos(2.0 * np.pi * b)
 
 

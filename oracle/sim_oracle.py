@@ -68,12 +68,12 @@ class Stream:
         return u01(r[0], r[1]), u01(r[2], r[3])
 
     def normal(self, index, tag):
-        """Box-Muller, cosine half (gst_kernel.hpp normal_from)."""
+        """Box-Muller, cosine half (gst_draws.h normal_from)."""
         a, b = self.uniform2(index, tag)
         return np.sqrt(-2.0 * np.log(1.0 - a)) * np.cos(2.0 * np.pi * b)
 
     def gamma(self, a, index, tag):
-        """Marsaglia-Tsang Gamma(a, 1) with paired attempts (gst_kernel.hpp gamma_mt)."""
+        """Marsaglia-Tsang Gamma(a, 1) with paired attempts (gst_draws.h gamma_mt)."""
         boost = 1.0
         if a < 1.0:
             ub, _ = self.uniform2(index, tag | 0xFFFFFF)

@@ -4,7 +4,7 @@ The GPU's theta posterior mean on ``ecq`` sits below the reference's long runs. 
 separate the GPU chain from the reference chain besides the kernel code itself:
 
 * the **samplers**: the kernel draws Gamma by Marsaglia-Tsang with the a+1 boost for a < 1
-  (``gst_kernel.hpp`` gamma_mt), the theta Beta as Ga / (Ga + Gb), normals by Box-Muller;
+  (``gst_draws.h`` gamma_mt), the theta Beta as Ga / (Ga + Gb), normals by Box-Muller;
   the reference uses numpy's legacy samplers (``scipy.stats.gamma/beta.rvs``,
   ``np.random.randn``; gibbs.py:97,130,180,196,239);
 * the **b draw**: the kernel draws b exactly (Cholesky, plus the SVD-floor rule where
@@ -45,7 +45,7 @@ class KernelSamplerVariates:
     * jumps and b normals: Box-Muller on (1 - u1, u2) (normal_pair);
     * Gamma(a): Marsaglia-Tsang, a < 1 via Gamma(a + 1) * (1 - u)^(1/a), attempts in pairs
       sharing one Box-Muller draw (gamma_mt);
-    * Beta(a, b) = Ga / (Ga + Gb) (the theta stage, gst_kernel.hpp:2362-2369);
+    * Beta(a, b) = Ga / (Ga + Gb) (the theta stage of gst_kernel.hpp);
     * Bernoulli: numpy's legacy inversion on one uniform (bern_legacy);
     * nu: choice on one uniform.
     """
@@ -101,7 +101,7 @@ class KernelSamplerVariates:
 
 
 def gamma_mt_vec(a, unif):
-    """gamma_mt (gst_kernel.hpp:479-510) for an array of shapes, vectorised over draws."""
+    """gamma_mt (gst_draws.h) for an array of shapes, vectorised over draws."""
     a = np.array(a, dtype=np.float64)
     out = np.empty_like(a)
     boost = np.ones_like(a)

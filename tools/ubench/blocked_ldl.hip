@@ -2,7 +2,7 @@
 // C layout (10 lower 16x16 tiles, lane l / reg g = row (l>>4) + 4g, col l & 15), panels of
 // 4 columns factored row-per-lane on the VALU, trailing rank-4 updates as
 // v_mfma_f64_16x16x4_f64.  The candidate replacement of the hyper block's 8x8-cyclic
-// register elimination (gst_kernel.hpp chol_range: ~16.5k cycles per 61-column
+// register elimination (gst_chol.hpp chol_range: ~16.5k cycles per 61-column
 // factorisation at one wave per SIMD, tools/stage_profile.py).
 //
 // Prints cycles per factorisation (s_memtime, one wave and two waves per SIMD) and the
