@@ -811,8 +811,22 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
   // likelihood they put an L2 round trip in front of each MH step's phi computation
   static_assert(RA - 8 * K0 <= 64, "one Fourier column per lane");
   const bool f_live = lane < RA - md.ntm_pad && lane < md.nf;
-  const double lfreq_l = f_live ? md.lfreq[lane] : 0.0;
-  const double ldf_l = f_live ? md.ldf[lane] : 0.0;
+  double lfreq_l = f_live ? md.lfreq[lane] : 0.0;
+  double ldf_l = f_live ? md.ldf[lane] : 0.0;
+  // OCC 2 (256 registers, no AGPRs): held across the sweep the two were spilled and each
+  // likelihood reloaded them from scratch right in front of its exp, a memory round trip with
+  // nothing behind it.  That build fetches them anew at the top of every MH step instead,
+  // ahead of the proposal and the prior, through bounded buffer resources (lanes that are not
+  // f_live read past the end and get the 0.0 they held before): hyper_lane_consts
+  const int hnlive = max(min(md.nf, RA - md.ntm_pad), 0);
+  auto hyper_lane_consts = [&]() __attribute__((always_inline)) {
+    if constexpr (OCC == 2) {
+      const double *plf = md.lfreq, *pldf = md.ldf;
+      asm volatile("" : "+s"(plf), "+s"(pldf));   // per step: not hoisted (and spilled) again
+      lfreq_l = lr_load(lane_rows(plf, hnlive, lane), 0);
+      ldf_l = lr_load(lane_rows(pldf, hnlive, lane), 0);
+    }
+  };
   // GEN: the ECORR epoch columns follow the Fourier block (lanes nf .. nf + nec - 1); the
   // lane's ecorr parameter index, or -1
   int geci = -1;
@@ -834,8 +848,8 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     // compiled to a cascade of scalar branches in front of every factorisation
     int iA = hidxA, ig = hidxg;
     asm("" : "+v"(iA), "+v"(ig));
-    const double lA = pget(xq, iA);
-    const double g = pget(xq, ig);
+    const double lA = pget_lane(xq, iA);
+    const double g = pget_lane(xq, ig);
     // log phi_k = 2 lA ln10 - log(12 pi^2) + (g-3) log fyr - g log f_k + log df_k
     const double lc = powerlaw_lc(lA, g, hl12, hlfyr);
     // S0 first: its 36 LDS loads are in flight while phi^-1 is computed (exp)
@@ -850,7 +864,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
       if (lane < RA - hntmp)
         phbuf[hntmp + lane] =
             f_live ? exp(-(lc - g * lfreq_l + ldf_l)) + fshift
-                   : (geci >= 0 ? exp(-2.0 * pget(xq, geci) * LN10) + fshift : 1.0);
+                   : (geci >= 0 ? exp(-2.0 * pget_lane(xq, geci) * LN10) + fshift : 1.0);
     } else {
       // every lane takes the exp (it sat in an exec-masked region of its own; the dummy
       // columns' lanes drop the value)
@@ -860,17 +874,29 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     // phbuf doubles as the eliminations' junk rows: restore the one other entry read
     // below, the augmented row's (no prior on the residual column)
     if (lane == 63) phbuf[raug] = 0.0;
-    // sum_k log phi_k in closed form (no reduction on the critical path)
-    double logdet_phi = logdet_phi_fourier(hnf, lc, g, hslf, hsldf, hldtm);
+    // sum_k log phi_k in closed form (no reduction on the critical path).  nf is converted
+    // to double here, from its scalar register: hoisted out of the sweep loop the converted
+    // value was spilled, and reloaded from scratch between the statistics and the verdict
+    int nfv = hnf;
+    asm volatile("" : "+s"(nfv));
+    double logdet_phi = logdet_phi_fourier(nfv, lc, g, hslf, hsldf, hldtm);
     if constexpr (GEN) {
       for (int b = 0; b < md.nb; ++b)   // log 10^(2 ecorr_b) per ECORR column of backend b
         if (md.ec_count[b] > 0.0)
           logdet_phi += logdet_phi_ecorr(md.ec_count[b], pget(xq, md.ecorr_b[b]));
     }
     lds_order();
+    // the prior on the diagonal: every lane reads its row's value (all loads in flight
+    // together) and the diagonal lanes keep the sum -- selects, not an exec-masked block of
+    // loads each waited for in turn
+    double phd[MT - K0];
 #pragma unroll
-    for (int r = K0; r < MT; ++r)
-      if (p == q) L[SL(r, r)] += phbuf[8 * r + p];
+    for (int r = K0; r < MT; ++r) phd[r - K0] = phbuf[8 * r + p];
+    // (opaque: a select fed directly by a load is turned back into a branch around the load)
+#pragma unroll
+    for (int r = K0; r < MT; ++r) asm("" : "+v"(phd[r - K0]));
+#pragma unroll
+    for (int r = K0; r < MT; ++r) L[SL(r, r)] = (p == q) ? L[SL(r, r)] + phd[r - K0] : L[SL(r, r)];
     CholCtx cc{colq, phbuf, colq2, lane, p, q, raug, 1.0, 0.0, 0, 0, {tm_apr, 1.0}, {tm_zr, 0.0}};
     GST_SUB_END(7)
     chol_range<MT, K0, RA, kp_for(OCC)>(L, cc);
@@ -1239,6 +1265,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
               kind = 3;
             }
           }
+          hyper_lane_consts();
           double xq[PX];
 #pragma unroll
           for (int t = 0; t < PX; ++t) xq[t] = role == 0 ? qa[t] : xv[t];
@@ -1324,9 +1351,11 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
       for (int pass = 0; pass < 2; ++pass) {
       gram_and_tm(xv);
       // the sweep's progress ticket (fair_prio), issued where only LDS and register work
-      // follows (the hyper MH): its return is awaited at the next sweep's start instead of by
-      // the next global load (taken at the sweep's start, the atomic's latency stalled the
-      // record / MH-variate stage; round-5 A/B: 20-sweep line +1%, 500 sweeps unchanged)
+      // follows (the hyper MH) and its value is used at the next sweep's start (taken at the
+      // sweep's start, the atomic's latency stalled the record / MH-variate stage; round-5
+      // A/B: 20-sweep line +1%, 500 sweeps unchanged).  In the OCC 2 build the return is still
+      // waited for here, once per sweep: the ticket is spilled, and the spill store needs it
+      // 
       if (OCC == 2 && st.prog && pass == 0 && lane == 0)
         prog_ret = __hip_atomic_fetch_add(st.prog, 1ull, __ATOMIC_RELAXED,
                                           __HIP_MEMORY_SCOPE_AGENT);
@@ -1336,6 +1365,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
 #pragma unroll 1
       for (int step = pass ? NHYPER : first; step <= NHYPER; ++step) {
         fair_prio<OCC>(fair);
+        hyper_lane_consts();
         double qv[PX], luacc = 0.0;
         if (step == NHYPER) {
           if (eval_only || !(mask & 4u)) break;

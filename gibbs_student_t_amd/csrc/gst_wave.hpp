@@ -201,6 +201,31 @@ __device__ __forceinline__ double pget(const double (&x)[8], int i) {
   return r;
 }
 
+// x[i] over a PER-LANE index (a VGPR), as one v_cmp + v_cndmask pair per candidate.  The
+// candidates are compared against opaque per-lane constants: over literal ones the compare
+// chain is recognised as a switch on i, and a switch on a divergent value is lowered to a
+// cascade of exec-mask regions (a saveexec and a branch per case, ~25 instructions a read in
+// front of every factorisation of the hyper MH).
+template <int N>
+__device__ __forceinline__ double pget_lane(const double (&x)[N], int i) {
+  double v[N];
+  int k[N - 1];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    v[j] = x[j];
+    asm("" : "+v"(v[j]));
+  }
+#pragma unroll
+  for (int j = 0; j < N - 1; ++j) {
+    k[j] = j;
+    asm("" : "+v"(k[j]));
+  }
+  double r = v[N - 1];
+#pragma unroll
+  for (int j = N - 2; j >= 0; --j) r = (i == k[j]) ? v[j] : r;
+  return r;
+}
+
 __device__ __forceinline__ int iget4(const int* a, int i) {   // a[i], i < 4
   return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3]));
 }
