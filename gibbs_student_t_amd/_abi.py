@@ -46,11 +46,14 @@ EXPORTS = ("gst_version", "gst_tape_stride", "gst_last_error", "gst_ctx_create",
            # ABI 6
            "gst_gram_counts", "gst_debug_variates",
            # ABI 7
-           "gst_set_accum")
+           "gst_set_accum",
+           # additive to ABI 7: found by symbol lookup
+           "gst_set_accum_toa")
 
 # entry points that older builds (A/B timing of library variants) may lack; calling one on
 # such a build raises AttributeError
-OPTIONAL = ("gst_set_debug", "gst_gram_counts", "gst_debug_variates", "gst_set_accum")
+OPTIONAL = ("gst_set_debug", "gst_gram_counts", "gst_debug_variates", "gst_set_accum",
+            "gst_set_accum_toa")
 
 _P = ct.POINTER
 _D = _P(ct.c_double)
@@ -98,6 +101,12 @@ class Accum(ct.Structure):
     _fields_ = [("z_sum", ct.c_void_p), ("pout_sum", ct.c_void_p), ("alpha_sum", ct.c_void_p),
                 ("b_sum", ct.c_void_p), ("b_sq", ct.c_void_p), ("count", ct.c_void_p),
                 ("from_sweep", ct.c_longlong)]
+
+
+class AccumToa(ct.Structure):
+    """gst_accum_toa: per-TOA exceedance counts of pout and the sums of y = r - T b."""
+    _fields_ = [("nthr", ct.c_int), ("thr", ct.c_double * 4), ("pout_gt", ct.c_void_p),
+                ("resid_sum", ct.c_void_p), ("resid_sq", ct.c_void_p)]
 
 
 class Tape(ct.Structure):
@@ -159,6 +168,8 @@ def load(path: str | None = None):
     lib.gst_sync.argtypes = [ct.c_void_p, ct.c_void_p]
     if hasattr(lib, "gst_set_accum"):
         lib.gst_set_accum.argtypes = [ct.c_void_p, _P(Accum)]
+    if hasattr(lib, "gst_set_accum_toa"):
+        lib.gst_set_accum_toa.argtypes = [ct.c_void_p, _P(AccumToa)]
     lib.gst_set_path.argtypes = [ct.c_void_p, ct.c_int]
     lib.gst_get_path.argtypes = [ct.c_void_p, _P(ct.c_int)]
     lib.gst_set_waves.argtypes = [ct.c_void_p, ct.c_int]

@@ -59,6 +59,10 @@ struct Ctx {
   // rewrites it in stream order
   gst_accum acc{};
   bool acc_on = false, acc_dirty = false;
+  // gst_set_accum_toa: the caller's descriptor (zero when unset; it rides in the same device
+  // copy) and the chain count its plane stride was last written for
+  gst_accum_toa acc_toa{};
+  int acc_C = 0;
   std::vector<void*> allocs;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -571,14 +575,19 @@ static int launch(Ctx* cx, const gst_state* s, const gst_records* r, const gst_t
   // posterior sums: sampling launches that reach from_sweep (never eval_only / GST_STAGE_GRAM)
   const bool acc_on = cx->acc_on && !eval_only && !(mask & GST_STAGE_GRAM) &&
                       sweep0 + nsweeps > cx->acc.from_sweep;
-  if (acc_on && cx->acc_dirty) {
+  // (pout_gt's plane stride is the launch's chain count times nmax)
+  if (acc_on && (cx->acc_dirty || (cx->acc_toa.pout_gt && C != cx->acc_C))) {
     const gst_accum& h = cx->acc;
+    const gst_accum_toa& t = cx->acc_toa;
     hipLaunchKernelGGL(set_accum_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
                        gst::accum_desc(cx->gram_cnt),
                        gst::DevAccum{h.z_sum, h.pout_sum, h.alpha_sum, h.b_sum, h.b_sq, h.count,
-                                     h.from_sweep});
+                                     h.from_sweep, t.pout_gt, t.resid_sum, t.resid_sq,
+                                     {t.thr[0], t.thr[1], t.thr[2], t.thr[3]},
+                                     (long long)C * cx->nmax, t.pout_gt ? t.nthr : 0});
     HIP_OK(hipGetLastError());
     cx->acc_dirty = false;
+    cx->acc_C = C;
   }
   gst::DevRec dr{};
   if (r) dr = gst::DevRec{r->x, r->b, r->z, r->alpha, r->pout, r->theta, r->nu, r->nrec};
@@ -636,6 +645,22 @@ int gst_set_accum(void* ctx, const gst_accum* acc) {
   if (!cx) return fail("gst_set_accum: null ctx");
   cx->acc_on = acc != nullptr;
   cx->acc = acc ? *acc : gst_accum{};
+  cx->acc_dirty = cx->acc_on;
+  return 0;
+}
+
+int gst_set_accum_toa(void* ctx, const gst_accum_toa* a) {
+  Ctx* cx = static_cast<Ctx*>(ctx);
+  if (!cx) return fail("gst_set_accum_toa: null ctx");
+  if (a) {
+    if (a->nthr < 0 || a->nthr > 4) return fail("gst_set_accum_toa: nthr must be 0..4");
+    for (int k = 0; k < a->nthr; ++k)
+      if (!(a->thr[k] > 0.0 && a->thr[k] < 1.0) || (k > 0 && !(a->thr[k] > a->thr[k - 1])))
+        return fail("gst_set_accum_toa: thresholds must be strictly increasing in (0, 1)");
+  }
+  cx->acc_toa = a ? *a : gst_accum_toa{};
+  if (cx->acc_toa.nthr == 0) cx->acc_toa.pout_gt = nullptr;
+  for (int k = cx->acc_toa.nthr; k < 4; ++k) cx->acc_toa.thr[k] = 0.0;
   cx->acc_dirty = cx->acc_on;
   return 0;
 }

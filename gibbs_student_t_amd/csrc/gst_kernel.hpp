@@ -1001,6 +1001,12 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
         double* const sz = A.z_sum;
         double* const sa = A.alpha_sum;
         double* const sp = A.pout_sum;
+        // gst_set_accum_toa: exceedance counts of pout at A.nthr thresholds (strict compare,
+        // a plane of A.gt_plane doubles per threshold) and the sums of y = r - T b and y^2;
+        // yv is the y of the b the sums above read (compute_Tb follows every b draw)
+        double* const sg = A.pout_gt;
+        double* const sy = A.resid_sum;
+        double* const sy2 = A.resid_sq;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
           const size_t e = (size_t)c * nst + 64 * s + lane;
@@ -1008,6 +1014,13 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
             if (sz) sz[e] += (double)((zb >> s) & 1u);
             if (sa) sa[e] += al[s];
             if (sp) sp[e] += po[s];
+            if (sg) {
+#pragma unroll 1
+              for (int k = 0; k < A.nthr; ++k)
+                sg[(size_t)k * A.gt_plane + e] += po[s] > A.thr[k] ? 1.0 : 0.0;
+            }
+            if (sy) sy[e] += yv[s];
+            if (sy2) sy2[e] += yv[s] * yv[s];
           }
         }
         if (lane == 0 && role == 0)

@@ -289,6 +289,26 @@ __global__ void __launch_bounds__(LBLK) lg_accum(const DevModel* __restrict__ md
     if (A.alpha_sum) A.alpha_sum[rt + t] += a.st.alpha[rt + t];
     if (A.pout_sum) A.pout_sum[rt + t] += a.st.pout[rt + t];
   }
+  // gst_set_accum_toa: exceedance counts of pout (strict compare) and the sums of y = r - T b
+  // and y^2; a.s.y is the y of the b read above (the plan's prologue lg_tb and each sweep's
+  // closing lg_tb; a sweep without the b stage leaves both alone)
+  if (A.pout_gt) {
+    for (int t = threadIdx.x; t < n; t += LBLK) {
+      const double p = a.st.pout[rt + t];
+      // (unrolled: a run-time index into the descriptor copy would put it in scratch)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < A.nthr) A.pout_gt[(size_t)k * A.gt_plane + rt + t] += p > A.thr[k] ? 1.0 : 0.0;
+    }
+  }
+  if (A.resid_sum || A.resid_sq) {
+    const double* yc = a.s.y + (size_t)c * a.ys;
+    for (int t = threadIdx.x; t < n; t += LBLK) {
+      const double y = yc[t];
+      if (A.resid_sum) A.resid_sum[rt + t] += y;
+      if (A.resid_sq) A.resid_sq[rt + t] += y * y;
+    }
+  }
   if (threadIdx.x == 0 && A.count) A.count[c] += 1;
 }
 

@@ -138,6 +138,13 @@ struct DevAccum {
   double *z_sum, *pout_sum, *alpha_sum, *b_sum, *b_sq;
   long long* count;
   long long from_sweep;
+  // gst_accum_toa (gst_set_accum_toa), all null / 0 when unset: exceedance counts of pout at
+  // nthr thresholds ([nthr] planes of gt_plane = C * nst doubles, C the launch's chains, which
+  // the host fills in per launch) and the sums of y = r - T b and y^2
+  double *pout_gt, *resid_sum, *resid_sq;
+  double thr[4];
+  long long gt_plane;
+  int nthr;
 };
 struct DevState {
   double *x, *b, *z, *alpha, *pout, *theta, *nu;

@@ -57,7 +57,12 @@ def _coll_device(device):
 
 
 def reduce_summary(vec_sum: np.ndarray, vec_max: np.ndarray, device=None):
-    """All-reduce per-rank summaries: sums (ESS, counts) and maxima (time, R-hat)."""
+    """All-reduce per-rank summaries: sums (ESS, counts) and maxima (time, R-hat).
+
+    ``post.PosteriorSums.pooled_vector()`` is such a sum: the reduced vector, read back with
+    ``from_pooled_vector``, holds the sums over all ranks' chains -- the exceedance counts of
+    the median rule and the residual sums of the signal band included, when they were kept
+    (every rank with the same thresholds)."""
     import torch
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()):

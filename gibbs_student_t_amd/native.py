@@ -18,6 +18,17 @@ MODEL_CODES = {"gaussian": _abi.GST_MODEL_GAUSSIAN, "t": _abi.GST_MODEL_T,
 STATE_KEYS = ("x", "b", "z", "alpha", "pout", "theta", "nu")
 # gst_accum's buffers, in the struct's order
 ACCUM_KEYS = ("z_sum", "pout_sum", "alpha_sum", "b_sum", "b_sq", "count")
+# gst_accum_toa's buffers, in the struct's order (allocated on request)
+ACCUM_TOA_KEYS = ("pout_gt", "resid_sum", "resid_sq")
+
+
+def _check_thresholds(thr):
+    """pout thresholds as a tuple of floats: at most 4, strictly increasing, each in (0, 1)."""
+    thr = () if thr is None else tuple(float(v) for v in np.atleast_1d(thr))
+    if len(thr) > 4 or any(not 0.0 < v < 1.0 for v in thr) or \
+            any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError("pout_thresholds: at most 4 strictly increasing values in (0, 1)")
+    return thr
 
 
 def _torch():
@@ -152,6 +163,7 @@ class NativeSampler:
         self.state = None
         self.dataset = None
         self._accum = None
+        self._accum_toa = None
 
     def set_waves(self, waves="auto"):
         """Waves per chain of the persistent path's sampling launches (gst_set_waves):
@@ -231,38 +243,79 @@ class NativeSampler:
                   "pout": (self.n,), "theta": (), "nu": ()}
         return {k: torch.empty((self.C, nrec) + shapes[k], **f64) for k in keys}
 
-    # ---- posterior sums (gst_set_accum) ----------------------------------------------
-    def _accum_shapes(self):
-        return {"z_sum": (self.C, self.n), "pout_sum": (self.C, self.n),
-                "alpha_sum": (self.C, self.n), "b_sum": (self.C, self.m),
-                "b_sq": (self.C, self.m), "count": (self.C,)}
+    # ---- posterior sums (gst_set_accum, gst_set_accum_toa) ---------------------------
+    def _accum_shapes(self, nthr=None):
+        sh = {"z_sum": (self.C, self.n), "pout_sum": (self.C, self.n),
+              "alpha_sum": (self.C, self.n), "b_sum": (self.C, self.m),
+              "b_sq": (self.C, self.m), "count": (self.C,),
+              "resid_sum": (self.C, self.n), "resid_sq": (self.C, self.n)}
+        if nthr:
+            sh["pout_gt"] = (int(nthr), self.C, self.n)
+        return sh
 
-    def alloc_accum(self, keys=ACCUM_KEYS):
+    def alloc_accum(self, keys=ACCUM_KEYS, pout_thresholds=None):
         """Zeroed device tensors for the posterior sums: ``z_sum`` / ``pout_sum`` /
         ``alpha_sum`` [C, n], ``b_sum`` / ``b_sq`` [C, m] (float64) and ``count`` [C]
-        (int64).  Pass the dict (or a subset of it) to ``set_accum``."""
+        (int64); on request ``pout_gt`` [K, C, n] (K = len(pout_thresholds)) and
+        ``resid_sum`` / ``resid_sq`` [C, n].  Pass the dict (or a subset of it) to
+        ``set_accum``."""
         torch = _torch()
-        shapes = self._accum_shapes()
+        thr = _check_thresholds(pout_thresholds)
+        shapes = self._accum_shapes(len(thr))
         unknown = [k for k in keys if k not in shapes]
         if unknown:
-            raise ValueError(f"unknown accumulator(s) {unknown}; choose from {ACCUM_KEYS}")
+            if unknown == ["pout_gt"]:
+                raise ValueError("pout_gt needs pout_thresholds")
+            raise ValueError(f"unknown accumulator(s) {unknown}; choose from "
+                             f"{ACCUM_KEYS + ACCUM_TOA_KEYS}")
         return {k: torch.zeros(shapes[k], device=self.tdev,
                                dtype=torch.int64 if k == "count" else torch.float64)
                 for k in keys}
 
-    def set_accum(self, acc: dict, from_sweep: int = 0):
-        """Every later ``sweep`` adds the state at the start of each of its sweeps with global
-        index ``sweep0 + i >= from_sweep`` into ``acc`` (tensors from ``alloc_accum``; missing
-        keys are skipped), whatever ``record_every`` is, until ``clear_accum``.  The sampler
-        keeps ``acc`` referenced while it is set."""
+    def _check_accum(self, acc, thr):
         torch = _torch()
-        shapes = self._accum_shapes()
+        shapes = self._accum_shapes(len(thr))
         for k, t in acc.items():
             want = torch.int64 if k == "count" else torch.float64
             if k not in shapes or t.dtype != want or not t.is_contiguous() \
                     or t.device != self.tdev or tuple(t.shape) != shapes[k]:
                 raise ValueError(f"accumulator {k!r}: need a contiguous {want} tensor of shape "
                                  f"{shapes.get(k)} on {self.tdev} (alloc_accum)")
+
+    def set_accum_toa(self, acc, pout_thresholds=None):
+        """gst_set_accum_toa alone: the ``pout_gt`` / ``resid_sum`` / ``resid_sq`` tensors of
+        ``acc`` (None or none of them: off).  They are added to only while ``set_accum`` is
+        set, from its ``from_sweep`` on."""
+        thr = _check_thresholds(pout_thresholds)
+        toa = {k: acc[k] for k in ACCUM_TOA_KEYS if acc and k in acc}
+        if not hasattr(self.lib, "gst_set_accum_toa"):
+            if toa:
+                raise _abi.GstNativeError("this libgst.so lacks gst_set_accum_toa; rebuild")
+            return
+        if "pout_gt" in toa and not thr:
+            raise ValueError("pout_gt needs pout_thresholds")
+        self._check_accum(toa, thr)
+        if not toa:
+            _abi.check(self.lib, self.lib.gst_set_accum_toa(self.ctx, None), "gst_set_accum_toa")
+            self._accum_toa = None
+            return
+        ptr = lambda k: ct.c_void_p(toa[k].data_ptr()) if k in toa else None  # noqa: E731
+        K = len(thr) if "pout_gt" in toa else 0
+        a = _abi.AccumToa(K, (ct.c_double * 4)(*thr[:K]), *(ptr(k) for k in ACCUM_TOA_KEYS))
+        _abi.check(self.lib, self.lib.gst_set_accum_toa(self.ctx, ct.byref(a)),
+                   "gst_set_accum_toa")
+        self._accum_toa = toa
+
+    def set_accum(self, acc: dict, from_sweep: int = 0, pout_thresholds=None):
+        """Every later ``sweep`` adds the state at the start of each of its sweeps with global
+        index ``sweep0 + i >= from_sweep`` into ``acc`` (tensors from ``alloc_accum``; missing
+        keys are skipped), whatever ``record_every`` is, until ``clear_accum``.  With
+        ``pout_gt`` in ``acc``, plane k counts the sweeps with ``pout > pout_thresholds[k]``
+        (up to 4 strictly increasing values in (0, 1)).  The sampler keeps ``acc`` referenced
+        while it is set."""
+        thr = _check_thresholds(pout_thresholds)
+        self._check_accum(acc, thr)
+        self.set_accum_toa(acc, thr)
         ptr = lambda k: ct.c_void_p(acc[k].data_ptr()) if k in acc else None  # noqa: E731
         a = _abi.Accum(*(ptr(k) for k in ACCUM_KEYS), int(from_sweep))
         _abi.check(self.lib, self.lib.gst_set_accum(self.ctx, ct.byref(a)), "gst_set_accum")
@@ -271,7 +324,10 @@ class NativeSampler:
     def clear_accum(self):
         """Stop accumulating (launches already queued on the stream still add)."""
         _abi.check(self.lib, self.lib.gst_set_accum(self.ctx, None), "gst_set_accum")
+        if hasattr(self.lib, "gst_set_accum_toa"):
+            _abi.check(self.lib, self.lib.gst_set_accum_toa(self.ctx, None), "gst_set_accum_toa")
         self._accum = None
+        self._accum_toa = None
 
     # ---- launches ------------------------------------------------------------------
     def stream_ptr(self):

@@ -6,34 +6,58 @@ and the signal ``T @ bchain`` (gibbs_likelihood.ipynb).  ``PosteriorSums`` holds
 those averages need -- per chain, so that chains, successive ``Gibbs.sample`` calls and
 ranks merge by addition -- without any per-TOA chain array.
 
+Two of the notebook's products are no mean (include/gst.h gst_accum_toa): its outlier rule
+``np.median(poutchain, axis=0) > tau``, which the per-TOA counts of the sweeps with
+``pout_t > tau`` decide exactly, and the band of the signal ``np.dot(Tmat, bchain[ind, :])``
+at every TOA, which the sums of ``y = r - T b`` and ``y^2`` give (r is constant:
+``E[T b] = r - E[y]``, ``Var[T b] = Var[y]``).
+
 All arrays are host numpy arrays with a leading chain axis: ``count`` [C] (int64),
-``z_sum`` / ``pout_sum`` / ``alpha_sum`` [C, n], ``b_sum`` / ``b_sq`` [C, m]; a sum that
-was not kept is ``None``.
+``z_sum`` / ``pout_sum`` / ``alpha_sum`` [C, n], ``b_sum`` / ``b_sq`` [C, m],
+``resid_sum`` / ``resid_sq`` [C, n]; ``pout_gt`` is [K, C, n], one plane per threshold of
+``pout_thr`` [K]; a sum that was not kept is ``None``.
 """
 from __future__ import annotations
 
 import numpy as np
 
 SUM_KEYS = ("z_sum", "pout_sum", "alpha_sum", "b_sum", "b_sq")
+# the sums of gst_accum_toa: after SUM_KEYS wherever the sums are listed in order, so that
+# a PosteriorSums without them looks (pooled vector, files) as it always did
+TOA_KEYS = ("pout_gt", "resid_sum", "resid_sq")
 
 
 class PosteriorSums:
-    def __init__(self, count, z_sum=None, pout_sum=None, alpha_sum=None, b_sum=None, b_sq=None):
+    def __init__(self, count, z_sum=None, pout_sum=None, alpha_sum=None, b_sum=None, b_sq=None,
+                 pout_thr=None, pout_gt=None, resid_sum=None, resid_sq=None):
         self.count = np.atleast_1d(np.asarray(count, dtype=np.int64))
         C = self.count.shape[0]
-        for key, v in zip(SUM_KEYS, (z_sum, pout_sum, alpha_sum, b_sum, b_sq)):
+        for key, v in zip(SUM_KEYS + TOA_KEYS[1:],
+                          (z_sum, pout_sum, alpha_sum, b_sum, b_sq, resid_sum, resid_sq)):
             if v is not None:
                 v = np.asarray(v, dtype=np.float64)
                 if v.ndim != 2 or v.shape[0] != C:
                     raise ValueError(f"{key}: need [C = {C}, ...], got {v.shape}")
             setattr(self, key, v)
+        if (pout_gt is None) != (pout_thr is None):
+            raise ValueError("pout_gt and pout_thr go together")
+        if pout_gt is not None:
+            pout_thr = np.atleast_1d(np.asarray(pout_thr, dtype=np.float64))
+            pout_gt = np.asarray(pout_gt, dtype=np.float64)
+            if pout_gt.ndim != 3 or pout_gt.shape[:2] != (pout_thr.shape[0], C):
+                raise ValueError(f"pout_gt: need [K = {pout_thr.shape[0]}, C = {C}, n], "
+                                 f"got {pout_gt.shape}")
+        self.pout_thr, self.pout_gt = pout_thr, pout_gt
 
     @classmethod
-    def from_device(cls, acc: dict):
-        """From ``NativeSampler.alloc_accum`` tensors (synchronises the device)."""
+    def from_device(cls, acc: dict, pout_thresholds=None):
+        """From ``NativeSampler.alloc_accum`` tensors (synchronises the device);
+        ``pout_thresholds``: the thresholds of ``acc["pout_gt"]``'s planes."""
         host = {k: v.detach().cpu().numpy() for k, v in acc.items()}
         if "count" not in host:
             raise ValueError("the accumulators need 'count'")
+        if "pout_gt" in host:
+            host["pout_thr"] = pout_thresholds
         return cls(**host)
 
     @property
@@ -79,16 +103,75 @@ class PosteriorSums:
             raise ValueError("z_mean_se needs at least two chains")
         return self.z_mean(pool=False).std(axis=0, ddof=1) / np.sqrt(self.nchains)
 
-    def outliers(self, threshold=0.9):
-        """Indices of the TOAs with mean z above ``threshold``: the notebook's
-        ``np.flatnonzero(zchain.mean(axis=0) > 0.9)``."""
-        return np.flatnonzero(self.z_mean() > threshold)
+    def outliers(self, threshold=0.9, rule="mean"):
+        """Indices of the outlier TOAs.  ``rule="mean"``: mean z above ``threshold``, the
+        notebook's ``np.flatnonzero(zchain.mean(axis=0) > 0.9)``.  ``rule="median"``: its
+        ``np.flatnonzero(np.median(poutchain, axis=0) > threshold)`` over all chains' sweeps,
+        from the exceedance counts (``threshold`` must be one of ``pout_thr``); a TOA that the
+        counts cannot decide (``pout_median_gt``) is an error, never a guess."""
+        if rule == "mean":
+            return np.flatnonzero(self.z_mean() > threshold)
+        if rule != "median":
+            raise ValueError("rule must be 'mean' or 'median'")
+        gt, amb = self.pout_median_gt(threshold)
+        if amb.any():
+            raise ValueError(f"median rule undecided at TOAs {np.flatnonzero(amb).tolist()}: "
+                             "exactly half of an even number of sweeps exceed the threshold "
+                             "(see pout_median_gt)")
+        return np.flatnonzero(gt)
 
     def signal_mean(self, T):
         """Posterior mean of the signal T b (the mean of ``T @ bchain`` over the sweeps)."""
         return np.asarray(T, dtype=np.float64) @ self.b_mean()
 
+    # ---- exceedance counts: the median rule ------------------------------------------
+    def _plane(self, thr):
+        gt = self._get("pout_gt")
+        k = np.flatnonzero(self.pout_thr == float(thr))
+        if k.size == 0:
+            raise ValueError(f"threshold {thr!r} was not kept; kept: {self.pout_thr.tolist()}")
+        return gt[k[0]]
+
+    def pout_exceed_frac(self, thr, pool=True):
+        """Fraction of the counted sweeps with ``pout_t > thr`` (strict): [n], or [C, n] per
+        chain.  ``thr`` must be one of the kept thresholds ``pout_thr``."""
+        g = self._plane(thr)
+        if pool:
+            return g.sum(axis=0) / self.count.sum()
+        return g / self.count[:, None]
+
+    def pout_median_gt(self, thr):
+        """``(decision, ambiguous)``, two boolean [n] arrays: whether the median of pout_t
+        over all chains' counted sweeps exceeds ``thr``, exactly as
+        ``np.median(poutchain, axis=0) > thr`` decides it.  With N sweeps and k of them above
+        ``thr`` the median is above for 2 k > N and not above for 2 k < N; for 2 k == N (even
+        N) the median is the mean of a value above and a value not above ``thr``, which
+        counts cannot place: those TOAs are marked ``ambiguous`` (their decision is False)."""
+        k = np.rint(self._plane(thr).sum(axis=0)).astype(np.int64)
+        N = int(self.count.sum())
+        return 2 * k > N, 2 * k == N
+
+    # ---- residual sums: the signal at every TOA --------------------------------------
+    def signal_mean_toa(self, r):
+        """Posterior mean of the signal T b at every TOA, ``r - E[y]`` with ``r`` the
+        residuals the model was built from: the centre of the notebook's waveform figure."""
+        return np.asarray(r, dtype=np.float64) - self._mean("resid_sum", True)
+
+    def signal_sd(self, pool=True):
+        """Standard deviation of the signal T b at every TOA over the counted sweeps
+        (population form; Var[T b] = Var[y] = E y^2 - (E y)^2): [n], or [C, n] per chain."""
+        m = self._mean("resid_sum", pool)
+        return np.sqrt(np.maximum(self._mean("resid_sq", pool) - m * m, 0.0))
+
     # ---- merging -------------------------------------------------------------------
+    def _same_kept(self, other):
+        for key in SUM_KEYS + TOA_KEYS:
+            if (getattr(self, key) is None) != (getattr(other, key) is None):
+                raise ValueError(f"{key} is kept by one operand only")
+        if self.pout_gt is not None and not np.array_equal(self.pout_thr, other.pout_thr):
+            raise ValueError(f"pout thresholds differ: {self.pout_thr.tolist()} and "
+                             f"{other.pout_thr.tolist()}")
+
     def __add__(self, other):
         """Sums of the same chains over more sweeps (successive ``sample`` calls)."""
         if not isinstance(other, PosteriorSums):
@@ -96,59 +179,84 @@ class PosteriorSums:
         if other.count.shape != self.count.shape:
             raise ValueError(f"chain counts differ: {self.nchains} and {other.nchains}; "
                              "use concat() for other chains")
-        kw = {}
-        for key in SUM_KEYS:
-            a, b = getattr(self, key), getattr(other, key)
-            if (a is None) != (b is None):
-                raise ValueError(f"{key} is kept by one operand only")
-            kw[key] = None if a is None else a + b
-        return PosteriorSums(self.count + other.count, **kw)
+        self._same_kept(other)
+        kw = {key: None if getattr(self, key) is None else getattr(self, key) + getattr(other, key)
+              for key in SUM_KEYS + TOA_KEYS}
+        return PosteriorSums(self.count + other.count, pout_thr=self.pout_thr, **kw)
 
     def concat(self, other):
         """Sums of other chains of the same model (another rank's shard) appended."""
+        self._same_kept(other)
         kw = {}
-        for key in SUM_KEYS:
+        for key in SUM_KEYS + TOA_KEYS:
             a, b = getattr(self, key), getattr(other, key)
-            if (a is None) != (b is None):
-                raise ValueError(f"{key} is kept by one operand only")
-            kw[key] = None if a is None else np.concatenate([a, b])
-        return PosteriorSums(np.concatenate([self.count, other.count]), **kw)
+            kw[key] = None if a is None else np.concatenate([a, b], axis=a.ndim - 2)
+        return PosteriorSums(np.concatenate([self.count, other.count]), pout_thr=self.pout_thr,
+                             **kw)
+
+    def select(self, chains, n=None):
+        """The sums of the chains ``chains`` (indices or a slice), per-TOA arrays cut to their
+        first ``n`` entries (a batch's dataset with fewer TOAs than the batch's stride)."""
+        kw = {}
+        for key in SUM_KEYS + TOA_KEYS:
+            v = getattr(self, key)
+            if v is not None:
+                v = v[..., chains, :]
+                if n is not None and key not in ("b_sum", "b_sq"):
+                    v = v[..., :n]
+            kw[key] = v
+        return PosteriorSums(self.count[chains], pout_thr=self.pout_thr, **kw)
 
     # ---- pooled form (what ranks exchange) -------------------------------------------
     def pooled(self):
         """The sums over this object's chains as one pseudo-chain ``PosteriorSums`` (C = 1):
         every pooled mean is unchanged, and pooled sums of several ranks merge with ``+``."""
-        kw = {k: None if getattr(self, k) is None else getattr(self, k).sum(axis=0, keepdims=True)
-              for k in SUM_KEYS}
-        return PosteriorSums([self.count.sum()], **kw)
+        kw = {}
+        for k in SUM_KEYS + TOA_KEYS:
+            v = getattr(self, k)
+            kw[k] = None if v is None else v.sum(axis=v.ndim - 2, keepdims=True)
+        return PosteriorSums([self.count.sum()], pout_thr=self.pout_thr, **kw)
 
     def pooled_vector(self):
         """``pooled()`` as one flat float64 vector [total count | the kept sums in SUM_KEYS
-        order]: what ``dist.reduce_summary`` adds over the ranks (counts stay exact below
-        2^53)."""
+        order | pout_gt plane by plane, resid_sum, resid_sq where kept]: what
+        ``dist.reduce_summary`` adds over the ranks (counts stay exact below 2^53)."""
         p = self.pooled()
         parts = [p.count.astype(np.float64)]
         parts += [getattr(p, k)[0] for k in SUM_KEYS if getattr(p, k) is not None]
+        if p.pout_gt is not None:
+            parts.append(p.pout_gt.reshape(-1))
+        parts += [getattr(p, k)[0] for k in TOA_KEYS[1:] if getattr(p, k) is not None]
         return np.concatenate(parts)
 
     def from_pooled_vector(self, vec):
         """A reduced ``pooled_vector()`` back as a C = 1 ``PosteriorSums`` with this object's
-        kept sums and sizes."""
+        kept sums, thresholds and sizes."""
         vec = np.asarray(vec, dtype=np.float64)
         kw, o = {}, 1
-        for k in SUM_KEYS:
-            if getattr(self, k) is not None:
-                w = getattr(self, k).shape[1]
+        for k in SUM_KEYS + TOA_KEYS:
+            v = getattr(self, k)
+            if v is None:
+                continue
+            w = v.shape[-1]
+            if k == "pout_gt":
+                K = v.shape[0]
+                kw[k] = vec[o:o + K * w].reshape(K, 1, w)
+                o += K * w
+            else:
                 kw[k] = vec[None, o:o + w]
                 o += w
         if o != vec.shape[0]:
             raise ValueError(f"vector of {vec.shape[0]} entries, expected {o}")
-        return PosteriorSums([int(round(vec[0]))], **kw)
+        return PosteriorSums([int(round(vec[0]))], pout_thr=self.pout_thr, **kw)
 
     # ---- files ---------------------------------------------------------------------
     def save(self, path):
         """A plain .npz (no pickles) of the arrays that were kept."""
-        arrays = {k: getattr(self, k) for k in SUM_KEYS if getattr(self, k) is not None}
+        arrays = {k: getattr(self, k) for k in SUM_KEYS + TOA_KEYS
+                  if getattr(self, k) is not None}
+        if self.pout_gt is not None:
+            arrays["pout_thr"] = self.pout_thr
         np.savez(path, count=self.count, **arrays)
 
     @classmethod

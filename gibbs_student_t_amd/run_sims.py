@@ -185,20 +185,56 @@ class Study:
         self.sweeps_done = 0
         self.vvh17_start = vvh17_start
         self.trapped = None
+        self.post = None                   # PosteriorSums of the last run(accumulate=True)
 
     @property
     def chain0(self):
         return self.entry0 * self.chains
 
     def run(self, niter, burn=100, outdir=None, chunk=500, record_every=1, keys=None,
-            progress=None):
+            progress=None, accumulate=False, pout_thresholds=None, signal_band=False):
         """Sample ``niter`` sweeps; write [burn:] records per entry under ``outdir``.
 
         Returns ``(records or None, seconds)``: without ``outdir`` the post-burn records
         are returned as host arrays ``{key: [E, chains, nrec, ...]}``.
-        """
-        ns, E, C = self.ns, len(self.entries), self.chains
+
+        ``keys`` restricts the recorded arrays (default: all of CHAIN_FILES; may be empty).
+        ``accumulate``: keep the posterior sums (post.PosteriorSums) of every sweep from
+        ``burn`` on, whatever ``record_every`` is -- with ``pout_thresholds`` the per-TOA
+        exceedance counts of pout, with ``signal_band`` the sums of y = r - T b and y^2 --
+        leave them in ``self.post`` (all chains, row stride ``ns.n``) and, with ``outdir``,
+        save each entry's as ``post.npz`` beside its chain files (its chains, per-TOA arrays
+        cut to its n)."""
+        ns, C = self.ns, self.chains
+        if (pout_thresholds is not None or signal_band) and not accumulate:
+            raise ValueError("pout_thresholds and signal_band need accumulate=True")
         keys = [k for k, _ in CHAIN_FILES] if keys is None else list(keys)
+        acc = None
+        if accumulate:
+            from .native import ACCUM_KEYS
+            extra = (("pout_gt",) if pout_thresholds is not None else ()) + \
+                (("resid_sum", "resid_sq") if signal_band else ())
+            acc = ns.alloc_accum(ACCUM_KEYS + extra, pout_thresholds=pout_thresholds)
+            ns.set_accum(acc, from_sweep=self.sweeps_done + int(burn),
+                         pout_thresholds=pout_thresholds)
+        try:
+            out = self._run(niter, burn, outdir, chunk, record_every, keys, progress)
+        finally:
+            if accumulate:
+                ns.clear_accum()
+        if accumulate:
+            from .post import PosteriorSums
+            self.post = PosteriorSums.from_device(acc, pout_thresholds)
+            if outdir is not None:
+                for i, e in enumerate(self.entries):
+                    d = e.outdir(outdir)
+                    os.makedirs(d, exist_ok=True)
+                    self.post.select(slice(i * C, (i + 1) * C), n=e.pta.n).save(
+                        os.path.join(d, "post.npz"))
+        return out
+
+    def _run(self, niter, burn, outdir, chunk, record_every, keys, progress):
+        ns, E, C = self.ns, len(self.entries), self.chains
         every = max(1, int(record_every))
         nrec_total = (niter + every - 1) // every
         first = (burn + every - 1) // every            # first kept record index
@@ -223,7 +259,7 @@ class Study:
         while done < niter:
             k = min(chunk, niter - done)
             kr = (k + every - 1) // every
-            rec = ns.alloc_records(kr, keys=keys)
+            rec = ns.alloc_records(kr, keys=keys) if keys else None
             ns.sweep(k, records=rec, record_every=every, seed=self.seed,
                      sweep0=self.sweeps_done, chain0=self.chain0)
             self.sweeps_done += k
@@ -373,7 +409,21 @@ def main(argv=None):
     ap.add_argument("--vvh17-start", choices=("reference", "clean"), default="reference",
                     help="vvh17 initial outlier flags: the reference's z = 1 (gibbs.py:50-51, "
                          "default) or z = 0")
+    ap.add_argument("--keys", nargs="*", default=None, choices=[k for k, _ in CHAIN_FILES],
+                    help="the chain arrays to record and write (default: all; none given: no "
+                         "chain files)")
+    ap.add_argument("--post", action="store_true",
+                    help="keep the posterior sums on the device from --burn on and save each "
+                         "entry's as post.npz (post.PosteriorSums.load)")
+    ap.add_argument("--pout-thresholds", type=float, nargs="+", default=None,
+                    help="with --post: per-TOA counts of the sweeps with pout above each "
+                         "threshold (the notebook's median rule; up to 4, increasing, in (0, 1))")
+    ap.add_argument("--signal-band", action="store_true",
+                    help="with --post: sums of y = r - T b and y^2 (mean and spread of the "
+                         "signal at every TOA)")
     args = ap.parse_args(argv)
+    if (args.pout_thresholds is not None or args.signal_band) and not args.post:
+        ap.error("--pout-thresholds and --signal-band need --post")
     from . import dist
     rank, local, world = dist.init()
     dofs = tuple([None] + list(args.dofs)) if args.dofs else (None,)
@@ -388,7 +438,8 @@ def main(argv=None):
     st = Study(mine, chains=args.chains, device=local, seed=args.seed, entry0=rank * per,
                vvh17_start=args.vvh17_start)
     recs, secs = st.run(args.niter, burn=args.burn, outdir=args.outdir, chunk=args.chunk,
-                        record_every=args.record_every)
+                        record_every=args.record_every, keys=args.keys, accumulate=args.post,
+                        pout_thresholds=args.pout_thresholds, signal_band=args.signal_band)
     total = len(mine) * args.chains * args.niter
     print(json.dumps({"rank": rank, "entries": len(mine), "chains": args.chains,
                       "sweeps": args.niter, "vvh17_start": args.vvh17_start, "seconds": secs,
@@ -396,7 +447,7 @@ def main(argv=None):
     for row in st.trapped or []:
         if row["trapped_record_frac"] > 0:
             print(json.dumps({"rank": rank, "trapped": row}), flush=True)
-    if recs is not None and rank == 0:
+    if recs is not None and "x" in recs and rank == 0:
         for row in summarise(mine, recs, args.chains):
             print(json.dumps(row))
     st.close()

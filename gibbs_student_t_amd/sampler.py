@@ -5,7 +5,9 @@ libgst.so.  Extra keyword-only options: ``nchains`` (independent chains batched 
 chain arrays gain a leading chain axis when > 1), ``seed`` (Philox key), ``device``,
 ``record_every`` (thin the chain arrays) and ``chunk`` (sweeps per kernel launch);
 ``sample`` takes ``record`` (which chain arrays to keep), ``accumulate`` and ``burn`` (posterior
-sums kept on the device, left in ``self.post``: post.PosteriorSums).
+sums kept on the device, left in ``self.post``: post.PosteriorSums), and with them
+``pout_thresholds`` (per-TOA counts of pout above each threshold: the notebook's median rule)
+and ``signal_band`` (sums of y = r - T b and y^2: the signal's spread at every TOA).
 
 Differences from the reference, all documented in DESIGN.md:
 * ``update_b`` recomputes T^T N^-1 T from the current state; the reference reuses whatever
@@ -202,7 +204,8 @@ class Gibbs:
         return self._ret(self._stage(xs, _abi.STAGE_DF)["nu"])
 
     # ---- the sampler (gibbs.py:342-385) ----------------------------------------------------
-    def sample(self, xs, niter=10000, *, record=None, accumulate=False, burn=0):
+    def sample(self, xs, niter=10000, *, record=None, accumulate=False, burn=0,
+               pout_thresholds=None, signal_band=False):
         """gibbs.py:342-385.  ``record``: the chain arrays to keep, a subset of ("x", "b",
         "z", "alpha", "pout", "theta", "nu") (default: all, as the reference); an omitted array
         is allocated neither on the host nor on the device, is not copied, and its attribute
@@ -210,7 +213,14 @@ class Gibbs:
         sweeps on the device, from its sweep ``burn`` on and on every sweep whatever
         ``record_every`` is, and leave them in ``self.post`` (post.PosteriorSums); the sums of
         successive calls merge with ``+``.  With both, a long run of a large pulsar gets its
-        outlier probabilities without any per-TOA chain array."""
+        outlier probabilities without any per-TOA chain array.  With ``accumulate``,
+        ``pout_thresholds`` (up to 4 strictly increasing values in (0, 1)) also keeps, per TOA,
+        the number of sweeps with ``pout > threshold`` -- what the notebook's median rule
+        ``np.median(poutchain, axis=0) > tau`` needs (``post.outliers(tau, rule="median")``)
+        -- and ``signal_band`` the sums of y = r - T b and y^2, the mean and spread of the
+        signal at every TOA (``post.signal_mean_toa``, ``post.signal_sd``)."""
+        if (pout_thresholds is not None or signal_band) and not accumulate:
+            raise ValueError("pout_thresholds and signal_band need accumulate=True")
         C, P = self.nchains, len(self.params)
         n, mcols = len(self._residuals), self._b_all.shape[1]
         every = max(1, self.record_every)
@@ -229,8 +239,12 @@ class Gibbs:
         self._push(self._xs_all(xs))
         acc = None
         if accumulate:
-            acc = self._native.alloc_accum()
-            self._native.set_accum(acc, from_sweep=self._sweep_counter + int(burn))
+            from .native import ACCUM_KEYS
+            extra = (("pout_gt",) if pout_thresholds is not None else ()) + \
+                (("resid_sum", "resid_sq") if signal_band else ())
+            acc = self._native.alloc_accum(ACCUM_KEYS + extra, pout_thresholds=pout_thresholds)
+            self._native.set_accum(acc, from_sweep=self._sweep_counter + int(burn),
+                                   pout_thresholds=pout_thresholds)
         try:
             chunk = max(every, (self.chunk // every) * every)
             tstart = time.time()
@@ -261,7 +275,7 @@ class Gibbs:
         x = self._pull()
         if accumulate:
             from .post import PosteriorSums
-            self.post = PosteriorSums.from_device(acc)
+            self.post = PosteriorSums.from_device(acc, pout_thresholds)
         self._counter_at_sample = self._sweep_counter
         return x[0] if C == 1 else x
 

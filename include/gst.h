@@ -191,6 +191,30 @@ typedef struct gst_accum {
   long long from_sweep; /* global sweep index (sweep0 + i) of the first counted sweep */
 } gst_accum;
 
+/* Per-TOA posterior sums that no mean gives (additive to ABI 7: callers find
+ * gst_set_accum_toa by symbol lookup).  The notebook's outlier rule is a median,
+ * np.median(poutchain, axis=0) > tau, and median(pout_t) > tau is decided by how many sweeps
+ * had pout_t > tau: plane k of pout_gt counts the sweeps with pout_t > thr[k] (strict compare,
+ * counts held as doubles like z_sum: exact below 2^53).  resid_sum / resid_sq are the sums of
+ * y_t = (r - T b)_t and y_t * y_t of the sweep's start-of-sweep b: r is constant, so
+ * E[T b] = r - E[y] and Var[T b] = Var[y] at every TOA -- the waveform band of
+ * np.dot(Tmat, bchain[ind, :]).  DEVICE pointers, caller-owned and caller-zeroed, indexed by
+ * launch-local chain with row stride nmax; plane k of pout_gt starts at k * nchains * nmax
+ * (nchains of the gst_sweep call).  Any pointer may be NULL.  thr must be strictly increasing
+ * with every value in (0, 1), nthr in [0, 4].
+ * The semantics are gst_accum's and there is no second from_sweep or count: the sums are kept
+ * only while gst_set_accum is set, from its from_sweep on, on every counted sweep whatever
+ * record_every is, one owner per element as a plain sum = sum + v in sweep order (resid_sq:
+ * sum + y * y, which may be fused); entries t >= n are never touched; gst_eval_lnlike and
+ * GST_STAGE_GRAM launches never add.  With gst_set_accum unset nothing is written. */
+typedef struct gst_accum_toa {
+  int nthr;           /* thresholds in use, 0..4 */
+  double thr[4];      /* strictly increasing, each in (0, 1) */
+  double* pout_gt;    /* [nthr][C][nmax]  sweeps with pout_t > thr[k] */
+  double* resid_sum;  /* [C][nmax]  sum of y_t = (r - T b)_t */
+  double* resid_sq;   /* [C][nmax]  sum of y_t^2 */
+} gst_accum_toa;
+
 int gst_version(void);
 int gst_tape_stride(int n, int m);
 int gst_last_error(char* buf, size_t len);
@@ -241,6 +265,10 @@ int gst_eval_lnlike(void* ctx, const gst_state* state, int nchains, double* out_
 /* Posterior sums (gst_accum above): *acc is copied; NULL switches accumulation off.  Takes
  * effect from the next gst_sweep call, in stream order with it. */
 int gst_set_accum(void* ctx, const gst_accum* acc);
+
+/* Exceedance counts and residual sums (gst_accum_toa above): *a is copied; NULL switches them
+ * off.  Kept only while gst_set_accum is set; takes effect from the next gst_sweep call. */
+int gst_set_accum_toa(void* ctx, const gst_accum_toa* a);
 
 int gst_sync(void* ctx, void* stream);
 

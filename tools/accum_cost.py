@@ -8,8 +8,13 @@ timed with device events after a warm-up launch:
 
     off         no accumulators, no records
     accum       all six accumulators set, no records
+    accum_toa   sums + thresholds (K = 2) + band: the six, pout_gt at two thresholds and
+                resid_sum / resid_sq (gst_set_accum_toa; skipped on a library without it)
     rec_every10 z / alpha / pout / b recorded every 10th sweep on the device
     rec_full    ... every sweep (the large-path run cut to the sweeps whose records fit)
+
+GST_LIB=<another build's libgst.so> times that build with the same driver (a parent build for
+comparison; --large-repeats 3 gives the large-path rows a spread to compare against).
 
 Records are timed on the device only: the copy to the host that Gibbs.sample adds is not in
 these numbers.
@@ -28,12 +33,24 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 REC_KEYS = ("b", "z", "alpha", "pout")
 
 
-def timed(ns, S, *, accum=False, record_every=0, seed=1, warm=8):
+TOA_THR = (0.5, 0.9)     # the accum_toa row's K = 2 thresholds
+
+
+def has_toa(ns):
+    """The library under test has gst_set_accum_toa (a parent build given by GST_LIB may not)"""
+    return hasattr(ns.lib, "gst_set_accum_toa")
+
+
+def timed(ns, S, *, accum=False, toa=False, record_every=0, seed=1, warm=8):
     """ms per sweep of one S-sweep launch (device events), after a warm-up launch."""
     import torch
     ns.sweep(warm, seed=seed)
     acc = rec = None
-    if accum:
+    if accum and toa:
+        from gibbs_student_t_amd.native import ACCUM_KEYS, ACCUM_TOA_KEYS
+        acc = ns.alloc_accum(ACCUM_KEYS + ACCUM_TOA_KEYS, pout_thresholds=TOA_THR)
+        ns.set_accum(acc, from_sweep=warm, pout_thresholds=TOA_THR)
+    elif accum:
         acc = ns.alloc_accum()
         ns.set_accum(acc, from_sweep=warm)
     if record_every:
@@ -52,17 +69,24 @@ def timed(ns, S, *, accum=False, record_every=0, seed=1, warm=8):
 def measure(make, S, S_full, repeats=3):
     out = {}
     for label, kw, sweeps in (("off", {}, S), ("accum", dict(accum=True), S),
+                              ("accum_toa", dict(accum=True, toa=True), S),
                               ("rec_every10", dict(record_every=10), S),
                               ("rec_full", dict(record_every=1), S_full)):
         ms = []
         for _ in range(repeats):
             ns = make()
+            if kw.get("toa") and not has_toa(ns):
+                ns.close()
+                break
             ms.append(timed(ns, sweeps, **kw))
             ns.close()
-        out[label] = {"sweeps": sweeps, "ms_per_sweep": sorted(ms),
-                      "median_ms_per_sweep": float(np.median(ms))}
-    for label in ("accum", "rec_every10", "rec_full"):
-        out[label]["over_off"] = out[label]["median_ms_per_sweep"] / out["off"]["median_ms_per_sweep"]
+        if ms:
+            out[label] = {"sweeps": sweeps, "ms_per_sweep": sorted(ms),
+                          "median_ms_per_sweep": float(np.median(ms))}
+    for label in ("accum", "accum_toa", "rec_every10", "rec_full"):
+        if label in out:
+            out[label]["over_off"] = \
+                out[label]["median_ms_per_sweep"] / out["off"]["median_ms_per_sweep"]
     return out
 
 
@@ -72,6 +96,8 @@ def main():
     ap.add_argument("--large-chains", type=int, default=1024)
     ap.add_argument("--large-full-sweeps", type=int, default=20,
                     help="sweeps of the large path's full-record run (316 KB per chain-sweep)")
+    ap.add_argument("--large-repeats", type=int, default=1,
+                    help="repeats of each large-path row (3: a spread to compare builds against)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "accum_cost.json"))
     a = ap.parse_args()
     import bench
@@ -104,7 +130,8 @@ def main():
            "config2": dict(chains=wl["C"], n=int(wl["ptas"][0].n), path="persistent",
                            **measure(config2, a.sweeps, a.sweeps)),
            "j1643_like": dict(chains=C, n=int(pta.n), path="large",
-                              **measure(j1643, a.sweeps, a.large_full_sweeps, repeats=1))}
+                              **measure(j1643, a.sweeps, a.large_full_sweeps,
+                                        repeats=a.large_repeats))}
     print(json.dumps(res))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
