@@ -48,12 +48,12 @@ EXPORTS = ("gst_version", "gst_tape_stride", "gst_last_error", "gst_ctx_create",
            # ABI 7
            "gst_set_accum",
            # additive to ABI 7: found by symbol lookup
-           "gst_set_accum_toa")
+           "gst_set_accum_toa", "gst_model_set_procs")
 
 # entry points that older builds (A/B timing of library variants) may lack; calling one on
 # such a build raises AttributeError
 OPTIONAL = ("gst_set_debug", "gst_gram_counts", "gst_debug_variates", "gst_set_accum",
-            "gst_set_accum_toa")
+            "gst_set_accum_toa", "gst_model_set_procs")
 
 _P = ct.POINTER
 _D = _P(ct.c_double)
@@ -82,6 +82,15 @@ class ModelDesc(ct.Structure):
         ("nbackend", ct.c_int), ("backend", _I), ("efac_idx", _I), ("equad_idx", _I),
         ("ecorr_idx", _I), ("n_ecorr", ct.c_int), ("ecorr_backend", _I),
     ]
+
+
+NPROC_MAX = 3
+
+
+class ModelProcs(ct.Structure):
+    """gst_model_procs: the power-law processes of the Fourier block, [red | dm | chrom]."""
+    _fields_ = [("nproc", ct.c_int), ("ncol", ct.c_int * NPROC_MAX),
+                ("idx_log10_A", ct.c_int * NPROC_MAX), ("idx_gamma", ct.c_int * NPROC_MAX)]
 
 
 class State(ct.Structure):
@@ -159,6 +168,8 @@ def load(path: str | None = None):
     lib.gst_ctx_destroy.argtypes = [ct.c_void_p]
     lib.gst_model_set.argtypes = [ct.c_void_p, _P(ModelDesc)]
     lib.gst_model_set_batch.argtypes = [ct.c_void_p, _P(ModelDesc), ct.c_int]
+    if hasattr(lib, "gst_model_set_procs"):
+        lib.gst_model_set_procs.argtypes = [ct.c_void_p, _P(ModelDesc), _P(ModelProcs), ct.c_int]
     lib.gst_model_info.argtypes = [ct.c_void_p, _P(ct.c_int), _P(ct.c_int), _P(ct.c_int)]
     lib.gst_sweep.argtypes = [ct.c_void_p, _P(State), _P(Records), _P(Tape), ct.c_int,
                               ct.c_int, ct.c_longlong, ct.c_int, ct.c_uint, ct.c_ulonglong,

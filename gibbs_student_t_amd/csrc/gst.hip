@@ -321,7 +321,34 @@ static int same_structure(const gst_model_desc* a, const gst_model_desc* b) {
   return 1;
 }
 
-int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
+// The power-law processes of the Fourier block against the descriptor they split
+static int check_procs(const gst_model_desc* d, const gst_model_procs* pr) {
+  if (pr->nproc < 1 || pr->nproc > GST_NPROC_MAX)
+    return fail("gst_model_set_procs: nproc must be 1..3");
+  int sum = 0;
+  for (int p = 0; p < pr->nproc; ++p) {
+    if (pr->ncol[p] <= 0 || pr->ncol[p] % 2)
+      return fail("gst_model_set_procs: every ncol must be even and positive");
+    sum += pr->ncol[p];
+    bool hasA = false, hasG = false;
+    for (int j = 0; j < d->n_hyper; ++j) {
+      hasA = hasA || d->hyper_idx[j] == pr->idx_log10_A[p];
+      hasG = hasG || d->hyper_idx[j] == pr->idx_gamma[p];
+    }
+    if (!hasA || !hasG || pr->idx_log10_A[p] < 0 || pr->idx_log10_A[p] >= d->nparams ||
+        pr->idx_gamma[p] < 0 || pr->idx_gamma[p] >= d->nparams)
+      return fail("gst_model_set_procs: a process's log10_A / gamma index is not a hyper "
+                  "parameter");
+  }
+  if (sum != d->nfourier) return fail("gst_model_set_procs: the ncol do not sum to nfourier");
+  if (pr->idx_log10_A[0] != d->idx_log10_A || pr->idx_gamma[0] != d->idx_gamma)
+    return fail("gst_model_set_procs: process 0 must be the descriptor's log10_A / gamma");
+  return 0;
+}
+
+// gst_model_set_batch / gst_model_set_procs: procs null is the red noise alone
+static int model_set(void* ctx, const gst_model_desc* descs, const gst_model_procs* procs,
+                     int nd) {
   Ctx* cx = static_cast<Ctx*>(ctx);
   if (!cx || !descs || nd <= 0) return fail("gst_model_set_batch: null argument");
   HIP_OK(hipSetDevice(cx->device));
@@ -329,6 +356,7 @@ int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
   int nmax = 0;
   for (int i = 0; i < nd; ++i) {
     if (check_desc(&descs[i])) return -1;
+    if (procs && check_procs(&descs[i], procs)) return -1;
     if (!same_structure(&descs[0], &descs[i]))
       return fail("gst_model_set_batch: datasets differ in basis shape, parameters or MH "
                   "index sets (dataset " + std::to_string(i) + ")");
@@ -389,7 +417,8 @@ int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
   free_model(cx);
   std::vector<gst::DevModel> hmd(nd);
   for (int i = 0; i < nd; ++i)
-    if (upload_dataset(cx, gst::pack_dataset(&descs[i], ntm_pad, raug_pack, large ? 0 : MT, disjoint),
+    if (upload_dataset(cx, gst::pack_dataset(&descs[i], ntm_pad, raug_pack, large ? 0 : MT, disjoint,
+                                             procs),
                        hmd[i])) {
       free_model(cx);
       return -1;
@@ -426,7 +455,16 @@ int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
 }
 
 
-int gst_model_set(void* ctx, const gst_model_desc* d) { return gst_model_set_batch(ctx, d, 1); }
+int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int nd) {
+  return model_set(ctx, descs, nullptr, nd);
+}
+
+int gst_model_set_procs(void* ctx, const gst_model_desc* descs, const gst_model_procs* procs,
+                        int nd) {
+  return model_set(ctx, descs, procs, nd);
+}
+
+int gst_model_set(void* ctx, const gst_model_desc* d) { return model_set(ctx, d, nullptr, 1); }
 
 int gst_model_info(void* ctx, int* ndatasets, int* nmax, int* tape_stride) {
   Ctx* cx = static_cast<Ctx*>(ctx);

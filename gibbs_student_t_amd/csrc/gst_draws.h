@@ -247,6 +247,12 @@ GST_HD double logdet_phi_fourier(int nf, double lc, double g, double sum_lfreq, 
                                  double logdet_phi_tm) {
   return ((double)nf * lc - g * sum_lfreq + sum_ldf) + logdet_phi_tm;
 }
+// several power-law processes in the Fourier block: the closed form of one process over its own
+// ncol columns; log|phi| = sum over the processes + the timing model's constant (+ ECORR)
+GST_HD double logdet_phi_process(int ncol, double lc, double g, double sum_lfreq,
+                                 double sum_ldf) {
+  return (double)ncol * lc - g * sum_lfreq + sum_ldf;
+}
 GST_HD double logdet_phi_ecorr(double count, double lec) { return count * (2.0 * lec * LN10); }
 // lnL = -0.5 (log|N| + r^T N^-1 r) + 0.5 (d^T Sigma^-1 d - log|Sigma| - log|phi|)
 GST_HD double marginal_ll(double logdetN, double rNr, double quad, double ld_sigma,

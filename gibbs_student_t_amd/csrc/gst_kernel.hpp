@@ -835,18 +835,36 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     if (e >= 0 && e < md.nec && lane < RA - md.ntm_pad) geci = md.ecorr_b[md.ecb[e]];
   }
 
+  // GEN: the Fourier block may hold several power-law processes (DevModel::nproc: red | dm |
+  // chrom), each over its own run of columns.  The lane's own (log10_A, gamma) indices, fixed
+  // for the launch as geci is: lc and g of lnl_hyper are then per-lane values with no select
+  // inside the MH loop (lanes past the Fourier block keep process 0's)
+  int lane_iA = md.idx_logA, lane_ig = md.idx_gamma;
+  if constexpr (GEN) {
+    for (int pp = 1; pp < md.nproc; ++pp)
+      if (lane >= md.pcol[pp]) {
+        lane_iA = md.pidxA[pp];
+        lane_ig = md.pidxG[pp];
+      }
+  }
+
   // b-marginalised likelihood at xq (gibbs.py:288-329); factor left in L.
   // the descriptor scalars of lnl_hyper, read once for the launch (wave-uniform: scalar
   // registers), not at each of the ~11 calls per sweep
   const int hidxA = md.idx_logA, hidxg = md.idx_gamma, hntmp = md.ntm_pad, hnf = md.nf;
   const double hl12 = md.log_12pi2, hlfyr = md.log_fyr, hslf = md.sum_lfreq,
                hsldf = md.sum_ldf, hldtm = md.logdet_phi_tm;
+  const int hnproc = GEN ? md.nproc : 1;
   auto lnl_hyper = [&](const double (&xq)[PX], int& failed) __attribute__((always_inline)) -> double {
     GST_COUNT(16)
     GST_SUB_BEGIN
     // the parameter indices as per-lane values: over a wave-uniform index pget's selects
     // compiled to a cascade of scalar branches in front of every factorisation
     int iA = hidxA, ig = hidxg;
+    if constexpr (GEN) {
+      iA = lane_iA;
+      ig = lane_ig;
+    }
     asm("" : "+v"(iA), "+v"(ig));
     const double lA = pget_lane(xq, iA);
     const double g = pget_lane(xq, ig);
@@ -881,6 +899,17 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     asm volatile("" : "+s"(nfv));
     double logdet_phi = logdet_phi_fourier(nfv, lc, g, hslf, hsldf, hldtm);
     if constexpr (GEN) {
+      if (hnproc > 1) {
+        // several processes: one wave-uniform term each, lc and g read from the first lane of
+        // the process's columns
+        double ldp = 0.0;
+        for (int pp = 0; pp < hnproc; ++pp) {
+          const int l0 = md.pcol[pp];
+          ldp += logdet_phi_process(md.pcol[pp + 1] - l0, rdlane(lc, l0), rdlane(g, l0),
+                                    md.psum_lfreq[pp], md.psum_ldf[pp]);
+        }
+        logdet_phi = ldp + hldtm;
+      }
       for (int b = 0; b < md.nb; ++b)   // log 10^(2 ecorr_b) per ECORR column of backend b
         if (md.ec_count[b] > 0.0)
           logdet_phi += logdet_phi_ecorr(md.ec_count[b], pget(xq, md.ecorr_b[b]));

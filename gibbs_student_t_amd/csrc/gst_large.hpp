@@ -1185,9 +1185,31 @@ __device__ __forceinline__ double hyper_lc(const DevModel& md, double lA, double
 __device__ __forceinline__ double hyper_logdet_phi0(const DevModel& md, double lc, double g) {
   return ((double)md.nf * lc - g * md.sum_lfreq + md.sum_ldf) + md.logdet_phi_tm;
 }
+// several power-law processes in the Fourier block (md.nproc > 1: red | dm | chrom, each over
+// its own run of columns; gst_draws.h logdet_phi_process): process pp's gamma and lc at x, the
+// process of Fourier column jc, and the Fourier + timing-model part of log|phi|
+__device__ __forceinline__ double hyper_proc_lc(const DevModel& md, const XVec& x, int pp,
+                                                double& g) {
+  g = xget(x, md.pidxG[pp]);
+  return hyper_lc(md, xget(x, md.pidxA[pp]), g);
+}
+__device__ __forceinline__ int hyper_proc_of(const DevModel& md, int jc) {
+  return (jc >= md.pcol[1] ? 1 : 0) + (jc >= md.pcol[2] ? 1 : 0);
+}
+__device__ __forceinline__ double hyper_logdet_phi0_procs(const DevModel& md, const XVec& x) {
+  double ldp = 0.0;
+  for (int pp = 0; pp < md.nproc; ++pp) {
+    double g;
+    const double lc = hyper_proc_lc(md, x, pp, g);
+    ldp += logdet_phi_process(md.pcol[pp + 1] - md.pcol[pp], lc, g, md.psum_lfreq[pp],
+                              md.psum_ldf[pp]);
+  }
+  return ldp + md.logdet_phi_tm;
+}
 __device__ __forceinline__ double hyper_logdet_phi(const DevModel& md, const XVec& x, double lc,
                                                    double g) {
   double logdet_phi = hyper_logdet_phi0(md, lc, g);
+  if (md.nproc > 1) logdet_phi = hyper_logdet_phi0_procs(md, x);
   for (int b = 0; b < md.nb; ++b)   // log 10^(2 ecorr_b) per ECORR column of backend b
     if (md.ec_count[b] > 0.0)
       logdet_phi += md.ec_count[b] * (2.0 * xget(x, md.ecorr_b[b]) * LN10);
@@ -1195,7 +1217,13 @@ __device__ __forceinline__ double hyper_logdet_phi(const DevModel& md, const XVe
 }
 __device__ __forceinline__ double phi_inv_col(const DevModel& md, const XVec& x, int jc, double lc,
                                               double g, double fsh) {
-  if (jc < md.nf) return exp(-(lc - g * md.lfreq[jc] + md.ldf[jc])) + fsh;
+  if (jc < md.nf) {
+    if (md.nproc > 1) {   // a later process's column: its own lc and g
+      const int pp = hyper_proc_of(md, jc);
+      if (pp > 0) lc = hyper_proc_lc(md, x, pp, g);
+    }
+    return exp(-(lc - g * md.lfreq[jc] + md.ldf[jc])) + fsh;
+  }
   const int b = md.ecb[jc - md.nf];
   int pi = md.ecorr_b[0];
 #pragma unroll
@@ -1485,6 +1513,18 @@ __global__ void __launch_bounds__(LBLK) lg_hyper(const DevModel* __restrict__ md
       }
     }
     double logdet_phi = ((double)nfr * lc - g * md.sum_lfreq + md.sum_ldf) + md.logdet_phi_tm;
+    if (md.nproc > 1) {
+      // several power-law processes (red | dm | chrom): the later processes' columns again with
+      // their own lc and g, and log|phi| process by process (hyper_logdet_phi0_procs)
+      // (each column by the thread that wrote it above: no barrier between the two writes)
+      for (int f = tid; f < nfr; f += LBLK)
+        if (f >= md.pcol[1]) {
+          double gp;
+          const double lcp = hyper_proc_lc(md, q, hyper_proc_of(md, f), gp);
+          ph[f] = exp(-(lcp - gp * md.lfreq[f] + md.ldf[f])) + fsh;
+        }
+      logdet_phi = hyper_logdet_phi0_procs(md, q);
+    }
     for (int b = 0; b < md.nb; ++b)   // log 10^(2 ecorr_b) per ECORR column of backend b
       if (md.ec_count[b] > 0.0)
         logdet_phi += md.ec_count[b] * (2.0 * xget(q, md.ecorr_b[b]) * LN10);
@@ -2177,7 +2217,14 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
   const double ldf_l = (fl_ >= 0 && fl_ < nfr) ? md.ldf[fl_] : 0.0;
   const int pib = lane < nb ? md.ecorr_b[lane] : -1;
   const double ecc = lane < nb ? md.ec_count[lane] : 0.0;
-  const int iA = md.idx_logA, iG = md.idx_gamma;
+  // (several power-law processes, md.nproc > 1: the indices of the lane's own Fourier column's
+  // process, so lc and g below are per-lane values; every other lane keeps process 0's)
+  int iA = md.idx_logA, iG = md.idx_gamma;
+  for (int pp = 1; pp < md.nproc; ++pp)
+    if (fl_ >= md.pcol[pp]) {
+      iA = md.pidxA[pp];
+      iG = md.pidxG[pp];
+    }
   // epochs e: G_ee, the augmented-row entry z_e = G_{r,e} and the backend
 #pragma unroll
   for (int k = 0; k < EC_NEB; ++k) {
@@ -2202,6 +2249,16 @@ __global__ void __launch_bounds__(64 * he_wpb(MT), 2) lg_hyper_ecr(const DevMode
     const double lc = hyper_lc(md, xs.q[iA], g);
     ph[lane] = (fl_ >= 0 && fl_ < nfr) ? phi_inv_fourier(lc, g, lf_l, ldf_l, fsh) : 0.0;
     double logdet_phi = hyper_logdet_phi0(md, lc, g);
+    if (md.nproc > 1) {   // process by process, each at its own parameters
+      double ldp = 0.0;
+      for (int pp = 0; pp < md.nproc; ++pp) {
+        const double gp = xs.q[md.pidxG[pp]];
+        ldp += logdet_phi_process(md.pcol[pp + 1] - md.pcol[pp],
+                                  hyper_lc(md, xs.q[md.pidxA[pp]], gp), gp, md.psum_lfreq[pp],
+                                  md.psum_ldf[pp]);
+      }
+      logdet_phi = ldp + md.logdet_phi_tm;
+    }
     const double xb = pib >= 0 ? xs.q[pib] : 0.0;   // lane b: backend b's log10_ecorr
     const double tb_ = ecc > 0.0 ? logdet_phi_ecorr(ecc, xb) : 0.0;
 #pragma unroll

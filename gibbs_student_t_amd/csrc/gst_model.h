@@ -16,6 +16,7 @@ constexpr int NHYPER = 10;
 constexpr int PMAX = 16;   // sampled parameters (large path; the persistent kernel takes <= 4,
                            // its general-white-noise (GEN) instances <= 8)
 constexpr int NBMAX = 8;   // backends with their own white-noise / ECORR parameters
+constexpr int NPROC_MAX = 3;   // power-law processes of the Fourier block (GST_NPROC_MAX)
 GST_HOST_DEVICE constexpr int SL(int r, int s) { return r * (r + 1) / 2 + s; }
 
 // LDS of one CU (gfx950), the most one workgroup's static + dynamic LDS can take
@@ -127,6 +128,16 @@ struct DevModel {
   double sum_lfreq, sum_ldf;  // sum_k log f_k, sum_k log df_k (closed-form log|phi|)
   double log_fyr, log_12pi2;
   unsigned long long* stamps;  // diagnostic build only (GST_STAMPS): [C][GST_NSTAMP]
+  // power-law processes of the Fourier block (gst.h gst_model_procs: red | dm | chrom), behind
+  // every earlier field so that none moves.  Process p owns the Fourier columns
+  // [pcol[p], pcol[p + 1]), pcol[nproc] = nf, with its log10_A / gamma parameter indices and
+  // the sums of log f_k and log df_k over its own columns (lfreq / ldf hold each process's
+  // ladder; sum_lfreq / sum_ldf above stay the sums over the whole block, which one process
+  // reads).  Entries p >= nproc repeat process 0's indices with no columns and zero sums.
+  int nproc;
+  int pcol[NPROC_MAX + 1];
+  int pidxA[NPROC_MAX], pidxG[NPROC_MAX];
+  double psum_lfreq[NPROC_MAX], psum_ldf[NPROC_MAX];
 };
 
 // gst_accum (posterior sums, gst_set_accum): the context's device copy, which the accumulating

@@ -61,8 +61,19 @@ struct AugRow {
   }
 };
 
+// The Fourier block of a descriptor without gst_model_procs: the red noise alone
+inline gst_model_procs one_process(const gst_model_desc* d) {
+  gst_model_procs pr{};
+  pr.nproc = 1;
+  pr.ncol[0] = d->nfourier;
+  pr.idx_log10_A[0] = d->idx_log10_A;
+  pr.idx_gamma[0] = d->idx_gamma;
+  return pr;
+}
+
 // Common arrays: column maps, T in both layouts, residuals, variances, spectrum pieces
-inline AugRow pack_common(const gst_model_desc* d, PackedModel& p, int ntm_pad, int raug) {
+inline AugRow pack_common(const gst_model_desc* d, const gst_model_procs& pr, PackedModel& p,
+                          int ntm_pad, int raug) {
   const int n = d->n, m = d->m, nf = d->nfourier, ntm = d->ntm, nec = d->n_ecorr;
   const int mpad = round_up(raug + 1, 16), npad = 64 * ((n + 63) / 64);
   // internal column order: [TM | pad | Fourier | ECORR | r | pad]; reference order
@@ -82,15 +93,31 @@ inline AugRow pack_common(const gst_model_desc* d, PackedModel& p, int ntm_pad, 
     p.resid[t] = d->residuals[t];
     p.sig2[t] = d->toaerrs[t] * d->toaerrs[t];
   }
-  // red-noise spectrum pieces: log f_k and log df_k (df from f[::2], enterprise powerlaw)
+  // spectrum pieces: log f_k and log df_k (df from f[::2], enterprise powerlaw), process by
+  // process: each has its own ladder, so df restarts at its first pair (f_1 - 0)
   p.lfreq.resize(nf);
   p.ldf.resize(nf);
   p.md.sum_lfreq = p.md.sum_ldf = 0.0;
-  for (int k = 0; k < nf; ++k) {
-    p.lfreq[k] = std::log(d->ffreqs[k]);
-    const int pair = k / 2;
-    const double prev = pair == 0 ? 0.0 : d->ffreqs[2 * (pair - 1)];
-    p.ldf[k] = std::log(d->ffreqs[2 * pair] - prev);
+  p.md.nproc = pr.nproc;
+  for (int q = 0, k0 = 0; q < NPROC_MAX; ++q) {
+    const int nc = q < pr.nproc ? pr.ncol[q] : 0;
+    p.md.pcol[q] = k0;
+    p.md.pcol[q + 1] = k0 + nc;
+    p.md.pidxA[q] = q < pr.nproc ? pr.idx_log10_A[q] : pr.idx_log10_A[0];
+    p.md.pidxG[q] = q < pr.nproc ? pr.idx_gamma[q] : pr.idx_gamma[0];
+    p.md.psum_lfreq[q] = p.md.psum_ldf[q] = 0.0;
+    const double* ff = d->ffreqs + k0;
+    for (int k = 0; k < nc; ++k) {
+      p.lfreq[k0 + k] = std::log(ff[k]);
+      const int pair = k / 2;
+      const double prev = pair == 0 ? 0.0 : ff[2 * (pair - 1)];
+      p.ldf[k0 + k] = std::log(ff[2 * pair] - prev);
+    }
+    for (int k = k0; k < k0 + nc; ++k) {
+      p.md.psum_lfreq[q] += p.lfreq[k];
+      p.md.psum_ldf[q] += p.ldf[k];
+    }
+    k0 += nc;
   }
   for (int k = 0; k < nf; ++k) {
     p.md.sum_lfreq += p.lfreq[k];
@@ -317,11 +344,12 @@ inline void pack_params(const gst_model_desc* d, PackedModel& p) {
 // row; a persistent-kernel instance larger than the model leaves unit-prior dummy columns
 // between the Fourier block and the residual row.  MT: the persistent
 // kernel's matrix slots, 0 on the large path.  batch_disjoint: ecorr_disjoint of every
-// dataset of the batch (one hyper class per batch structure).
+// dataset of the batch (one hyper class per batch structure).  procs: the batch's power-law
+// processes (validated, gst.hip check_procs), or null for the red noise alone.
 inline PackedModel pack_dataset(const gst_model_desc* d, int ntm_pad, int raug, int MT,
-                                bool batch_disjoint) {
+                                bool batch_disjoint, const gst_model_procs* procs = nullptr) {
   PackedModel p;
-  const AugRow row = pack_common(d, p, ntm_pad, raug);
+  const AugRow row = pack_common(d, procs ? *procs : one_process(d), p, ntm_pad, raug);
   pack_classes(d, p);
   if (MT > 0 && p.md.ncls > 0) pack_class_grams(row, p, MT);
   pack_params(d, p);

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from .model import DAY_SEC, FYR, PulsarData, fourier_basis, powerlaw
+from .model import DAY_SEC, FYR, PulsarData, chromatic_basis, fourier_basis, powerlaw
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 J1713_NPZ = os.path.join(_HERE, "data", "J1713+0747.npz")
@@ -201,7 +201,8 @@ def scaled_synthetic(n: int = 100_000, components: int = 60, ntm: int = 300, see
 def multiband(nepochs: int = 60, nsub: int = 3, backends=("ASP", "GUPPI"), seed: int = 1643,
               theta: float = 0.05, sigma_out: float = 1e-6, efac=(1.1, 0.9),
               log10_equad=(-6.6, -7.0), log10_ecorr=(-6.5, -6.8), log10_A: float = -14.0,
-              gamma: float = 4.33, components: int = 10, nerr: int = 0) -> PulsarData:
+              gamma: float = 4.33, components: int = 10, nerr: int = 0, *,
+              band_mhz=None, dm=None) -> PulsarData:
     """A NANOGrav-style multi-backend, multi-band dataset for the general white-noise model
     of the notebook's J1643-1224 run (gibbs_likelihood.ipynb cell 2: efac, equad, ECORR per
     backend, power-law red noise, timing model) -- not in the reference's data, built with
@@ -213,7 +214,14 @@ def multiband(nepochs: int = 60, nsub: int = 3, backends=("ASP", "GUPPI"), seed:
     by an epoch's TOAs, power-law red noise, Bernoulli(theta) outliers, and the timing model
     projected out.  The per-backend true values are in ``meta``.  ``nerr`` > 0: every TOA's
     error bar is one of ``nerr`` values (a few noise classes per backend, as a receiver's
-    quantised template-fit errors give) instead of log-normal."""
+    quantised template-fit errors give) instead of log-normal.
+
+    ``band_mhz`` (``nsub`` values) gives the sub-bands' radio frequencies, tiled over the
+    epochs into ``freqs``.  ``dm=(log10_A, gamma, components)`` adds a realisation of
+    dispersion-measure variations, a power-law process on the Fourier basis scaled by
+    ``(1400 MHz / nu)^2`` (model.chromatic_basis), before the timing model is projected out; it
+    needs ``band_mhz`` and is drawn from a generator of its own, so the other draws are those
+    of the same call without it."""
     raw = load_j1713_raw()
     mjd0 = (raw["mjd_int"].astype(np.float64) + raw["mjd_frac"])[:nepochs]
     rng = np.random.default_rng(seed)
@@ -236,11 +244,25 @@ def multiband(nepochs: int = 60, nsub: int = 3, backends=("ASP", "GUPPI"), seed:
     white = np.sqrt((ef * err) ** 2 + 10 ** (2 * eq)) * rng.standard_normal(n)
     z = (rng.random(n) < theta).astype(np.int64)
     r = red + jitter + np.where(z == 1, sigma_out * rng.standard_normal(n), white)
+    freqs = None
+    meta = {"z_true": z, "seed": seed, "theta": theta, "efac": efac,
+            "log10_equad": log10_equad, "log10_ecorr": log10_ecorr, "epoch": ep}
+    if band_mhz is not None:
+        band = np.asarray(band_mhz, dtype=np.float64)
+        if band.shape != (nsub,):
+            raise ValueError("band_mhz: one frequency per sub-band")
+        freqs = np.tile(band, nepochs)
+    if dm is not None:
+        if freqs is None:
+            raise ValueError("dm needs band_mhz")
+        dm_A, dm_gamma, dm_nc = float(dm[0]), float(dm[1]), int(dm[2])
+        Fd, fd = chromatic_basis(toas, freqs, dm_nc, 2)
+        r = r + Fd @ (np.sqrt(powerlaw(fd, dm_A, dm_gamma))
+                      * np.random.default_rng([seed, 1]).standard_normal(2 * dm_nc))
+        meta["dm"] = (dm_A, dm_gamma, dm_nc)
     r = r - U @ (U.T @ r)
     return PulsarData(name="MB", toas=toas, residuals=r, toaerrs=err, Mmat=M, backends=labels,
-                      meta={"z_true": z, "seed": seed, "theta": theta, "efac": efac,
-                            "log10_equad": log10_equad, "log10_ecorr": log10_ecorr,
-                            "epoch": ep})
+                      freqs=freqs, meta=meta)
 
 
 __all__ = ["load_j1713_raw", "multiband", "scaled_synthetic", "design_matrix", "simulate_residuals", "j1713",

@@ -38,9 +38,18 @@ itself is **unpinned** (no fixture of it exists in the reference).  Everything e
 build -- the CPU oracle, the golden generator and the HIP path -- consumes this one model,
 so the sampler parity is exact with respect to it.
 
-Column order of the basis ``T`` is ``[Fourier (2*components) | timing model | ECORR]`` as in
-enterprise's signal-collection order ``ef + eq + rn + tm (+ ec)`` (run_sims.py:74,
-gibbs_likelihood.ipynb cell 2).
+* ``dm_gp=dict(components=, log10_A=(lo, hi), gamma=(lo, hi))`` / ``chrom_gp=...``:
+  dispersion-measure variations and a scattering-like chromatic process, each a second
+  power-law Fourier GP whose basis is scaled by ``(1400 MHz / nu)^2`` resp. ``^4``
+  (enterprise ``createfourierdesignmatrix_dm`` / ``_chromatic`` with ``utils.powerlaw``),
+  parameters ``{psr}_dm_gp_log10_A``, ``{psr}_dm_gp_gamma``, ``{psr}_chrom_gp_...``.  The
+  reference sampler takes every ``log10_A`` / ``gamma`` parameter as a hyper parameter
+  (gibbs.py:64-69) and asks the pta for ``phi``, so it runs such a model unchanged.
+
+Column order of the basis ``T`` is ``[Fourier (red | dm | chrom) | timing model | ECORR]`` as
+in enterprise's signal-collection order ``ef + eq + rn (+ dm) + tm (+ ec)`` (run_sims.py:74,
+gibbs_likelihood.ipynb cell 2); ``Ffreqs`` is each process's ``repeat(f, 2)`` in turn and
+``pta.procs`` describes the layout.
 """
 from __future__ import annotations
 
@@ -101,6 +110,36 @@ def fourier_basis(toas: np.ndarray, nmodes: int, Tspan: float | None = None):
     F[:, ::2] = np.sin(arg)
     F[:, 1::2] = np.cos(arg)
     return F, np.repeat(f, 2)
+
+
+# Power-law processes of the Fourier block beside the achromatic red noise, in basis order:
+# (PTA keyword, chromatic index chi).  Process p's basis is the red-noise Fourier basis scaled
+# TOA by TOA with (FREF_MHZ / nu_t)^chi (enterprise ``createfourierdesignmatrix_dm`` for
+# chi = 2, ``createfourierdesignmatrix_chromatic`` with idx = 4), its parameters are named
+# ``<psr>_<keyword>_log10_A`` / ``<psr>_<keyword>_gamma``.
+CHROMATIC_GPS = (("dm_gp", 2), ("chrom_gp", 4))
+FREF_MHZ = 1400.0
+
+
+@dataclass(frozen=True)
+class Process:
+    """One power-law process of the Fourier block: its columns of ``T`` (``col0`` ..
+    ``col0 + ncol``), chromatic index and the indices of its two parameters in ``params``."""
+
+    name: str          # "red", "dm_gp", "chrom_gp"
+    chi: int
+    components: int
+    col0: int
+    ncol: int
+    idx_log10_A: int
+    idx_gamma: int
+
+
+def chromatic_basis(toas, freqs, nmodes: int, chi: int, Tspan: float | None = None):
+    """Fourier design matrix of a chromatic process: ``fourier_basis`` with every row scaled by
+    ``(1400 MHz / nu_t)^chi``.  Returns ``(F, Ffreqs)``; the ladder is the process's own."""
+    F, ff = fourier_basis(toas, nmodes, Tspan)
+    return F * ((FREF_MHZ / np.asarray(freqs, dtype=np.float64)) ** chi)[:, None], ff
 
 
 def powerlaw(f: np.ndarray, log10_A: float, gamma: float, components: int = 2):
@@ -170,13 +209,23 @@ class PTA:
     def __init__(self, psr: PulsarData, components: int = 30, efac=1.0,
                  log10_equad=(-10.0, -5.0), log10_A=(-18.0, -12.0), gamma=(1.0, 7.0),
                  tm_weight: float = 1e40, Tspan: float | None = None, *,
-                 selection: str = "none", log10_ecorr=None, ecorr_dt: float = 1.0):
+                 selection: str = "none", log10_ecorr=None, ecorr_dt: float = 1.0,
+                 dm_gp=None, chrom_gp=None):
         self.psr = psr
         self.components = int(components)
         self._r = np.asarray(psr.residuals, dtype=np.float64)
         self._toaerrs = np.asarray(psr.toaerrs, dtype=np.float64)
         toas = np.asarray(psr.toas, dtype=np.float64)
         self.F, self.Ffreqs = fourier_basis(toas, self.components, Tspan)
+        # dispersion-measure / chromatic power laws: dict(components=, log10_A=(lo, hi),
+        # gamma=(lo, hi)); their columns follow the red noise's, T = [red | dm | chrom | ...]
+        self._gps = self._gp_specs(dm_gp=dm_gp, chrom_gp=chrom_gp)
+        for kw, chi, spec in self._gps:
+            if psr.freqs is None:
+                raise ValueError(f"{kw} needs psr.freqs (the TOAs' radio frequencies, MHz)")
+            Fp, ffp = chromatic_basis(toas, psr.freqs, spec["components"], chi, Tspan)
+            self.F = np.hstack([self.F, Fp])
+            self.Ffreqs = np.concatenate([self.Ffreqs, ffp])
         U, w = svd_tm_basis(np.asarray(psr.Mmat, dtype=np.float64))
         self.U = U
         self.tm_phi = w * tm_weight          # tm_prior (run_sims.py:27-29)
@@ -214,6 +263,23 @@ class PTA:
             self.backend_names = [""]
             self.bidx = np.zeros(n, dtype=np.int64)
 
+    @staticmethod
+    def _gp_specs(**gps):
+        """[(keyword, chi, dict(components, log10_A, gamma))] of the given chromatic processes,
+        in basis order, with the red noise's default priors filled in."""
+        out = []
+        for kw, chi in CHROMATIC_GPS:
+            spec = gps.get(kw)
+            if spec is None:
+                continue
+            unknown = set(spec) - {"components", "log10_A", "gamma"}
+            if unknown or "components" not in spec or int(spec["components"]) < 1:
+                raise ValueError(f"{kw}: dict(components=, log10_A=(lo, hi), gamma=(lo, hi))")
+            out.append((kw, chi, dict(components=int(spec["components"]),
+                                      log10_A=tuple(spec.get("log10_A", (-18.0, -12.0))),
+                                      gamma=tuple(spec.get("gamma", (1.0, 7.0))))))
+        return out
+
     def _pname(self, b, what):
         be = self.backend_names[b]
         return f"{self.psr.name}_{be}_{what}" if be else f"{self.psr.name}_{what}"
@@ -232,14 +298,28 @@ class PTA:
             plist += [Uniform(self._pname(b, "log10_ecorr"), *log10_ecorr) for b in range(nb)]
         plist.append(Uniform(f"{nm}_log10_A", *log10_A))
         plist.append(Uniform(f"{nm}_gamma", *gamma))
+        for kw, _, spec in self._gps:
+            plist.append(Uniform(f"{nm}_{kw}_log10_A", *spec["log10_A"]))
+            plist.append(Uniform(f"{nm}_{kw}_gamma", *spec["gamma"]))
         # enterprise returns params sorted by name
         self._params = sorted(plist, key=lambda p: p.name)
         self.has_ecorr = log10_ecorr is not None
+        # the layout of the Fourier block, process by process
+        names = [p.name for p in self._params]
+        self.procs, col0 = [], 0
+        for kw, chi, nc in [("red", 0, self.components)] + \
+                [(kw, chi, spec["components"]) for kw, chi, spec in self._gps]:
+            pre = f"{nm}_" if kw == "red" else f"{nm}_{kw}_"
+            self.procs.append(Process(kw, chi, nc, col0, 2 * nc, names.index(pre + "log10_A"),
+                                      names.index(pre + "gamma")))
+            col0 += 2 * nc
 
     @classmethod
     def from_arrays(cls, name, residuals, toaerrs, T, Ffreqs, components, tm_weight=1e40,
                     efac=1.0, **priors):
-        """Rebuild a model from stored arrays (golden fixtures) without re-deriving T."""
+        """Rebuild a model from stored arrays (golden fixtures) without re-deriving T.
+        ``components`` counts the red noise's; ``dm_gp`` / ``chrom_gp`` (keywords, as in the
+        constructor) say how the rest of the Fourier block of ``T`` / ``Ffreqs`` splits."""
         obj = cls.__new__(cls)
         obj.psr = PulsarData(name=str(name), toas=np.zeros(len(residuals)),
                              residuals=np.asarray(residuals), toaerrs=np.asarray(toaerrs),
@@ -247,7 +327,10 @@ class PTA:
         obj.components = int(components)
         obj._r = np.asarray(residuals, dtype=np.float64)
         obj._toaerrs = np.asarray(toaerrs, dtype=np.float64)
-        nf = 2 * obj.components
+        # the Fourier block: [red | dm | chrom], Ffreqs each process's ladder in turn
+        obj._gps = cls._gp_specs(dm_gp=priors.pop("dm_gp", None),
+                                 chrom_gp=priors.pop("chrom_gp", None))
+        nf = 2 * (obj.components + sum(spec["components"] for _, _, spec in obj._gps))
         T = np.asarray(T, dtype=np.float64)
         obj.F, obj.Ffreqs = T[:, :nf], np.asarray(Ffreqs, dtype=np.float64)
         obj.U = T[:, nf:]
@@ -299,9 +382,14 @@ class PTA:
         return [efac ** 2 * self._toaerrs ** 2 + 10 ** (2 * eq)]
 
     def get_phi(self, params):
-        pl = powerlaw(self.Ffreqs, self._value(params, "log10_A"),
+        pl = powerlaw(self.Ffreqs[:2 * self.components], self._value(params, "log10_A"),
                       self._value(params, "gamma"), components=2)
-        parts = [pl, self.tm_phi]
+        parts = [pl]
+        for pr in self.procs[1:]:   # each over its own ladder: df restarts at f_1 - 0
+            parts.append(powerlaw(self.Ffreqs[pr.col0:pr.col0 + pr.ncol],
+                                  self._value(params, f"{pr.name}_log10_A"),
+                                  self._value(params, f"{pr.name}_gamma"), components=2))
+        parts.append(self.tm_phi)
         if self.n_ecorr:
             ec = np.array([params[self._pname(b, "log10_ecorr")]
                            for b in range(len(self.backend_names))])
@@ -325,7 +413,7 @@ class PTA:
 
     @property
     def nfourier(self):
-        return 2 * self.components
+        return self.F.shape[1]
 
     @property
     def ntm(self):
@@ -346,8 +434,16 @@ class PTA:
                          else -1 for b in range(len(self.backend_names))], dtype=np.int64)
 
     def param_index(self, suffix):
-        for i, p in enumerate(self._params):
-            if p.name.endswith("_" + suffix):
+        """Index of the parameter ``<psr>_<suffix>``, else of the first whose name ends in
+        ``_<suffix>`` (per-backend names) and is not another process's (``dm_gp_log10_A``
+        sorts before ``log10_A``)."""
+        names = self.param_names
+        exact = f"{self.psr.name}_{suffix}"
+        if exact in names:
+            return names.index(exact)
+        for i, nm in enumerate(names):
+            if nm.endswith("_" + suffix) and \
+                    not any(nm.endswith(f"_{kw}_{suffix}") for kw, _ in CHROMATIC_GPS):
                 return i
         return -1
 
@@ -382,6 +478,7 @@ def mh_constants():
     return np.array([0.1, 0.15, 0.5, 0.15, 0.1]), np.array([0.1, 0.5, 1.0, 3.0, 10.0])
 
 
-__all__ = ["Constant", "Uniform", "PulsarData", "PTA", "fourier_basis", "powerlaw",
+__all__ = ["Constant", "Uniform", "PulsarData", "PTA", "Process", "fourier_basis",
+           "chromatic_basis", "powerlaw", "CHROMATIC_GPS", "FREF_MHZ",
            "svd_tm_basis", "quantization_matrix", "df_tables", "hyper_white_indices", "mh_constants",
            "FYR", "YR_SEC", "DAY_SEC"]

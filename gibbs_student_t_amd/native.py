@@ -40,12 +40,19 @@ def model_desc(pta, cfg: dict):
     """Build the gst_model_desc for a ``model.PTA`` and Gibbs kwargs (gibbs.py:9-11).
 
     Returns ``(desc, keepalive)``; keep ``keepalive`` referenced while ``desc`` is used.
+    ``keepalive["procs"]`` is the ``gst_model_procs`` of the model's Fourier block (``pta.procs``:
+    red | dm | chrom; one process for a pta without the attribute), which ``gst_model_set_procs``
+    takes beside the descriptors when there is more than one.
     """
     names = [p.name for p in pta.params]
     P = len(names)
     hind, wind = hyper_white_indices(names)
+    procs = list(getattr(pta, "procs", ()))
 
     def role(suffix):
+        # the red noise's pair by exact name: dm_gp_log10_A sorts before log10_A
+        if procs and suffix in ("log10_A", "gamma"):
+            return procs[0].idx_log10_A if suffix == "log10_A" else procs[0].idx_gamma
         for i, nm in enumerate(names):
             if nm.endswith("_" + suffix):
                 return i
@@ -108,6 +115,13 @@ def model_desc(pta, cfg: dict):
         desc.ecorr_idx = ip(keep["eci"])
         desc.n_ecorr = n_ec
         desc.ecorr_backend = ip(keep["ecb"]) if n_ec else None
+    if len(procs) > _abi.NPROC_MAX:
+        raise ValueError(f"at most {_abi.NPROC_MAX} power-law processes")
+    pr = _abi.ModelProcs(nproc=max(len(procs), 1))
+    pr.ncol[0], pr.idx_log10_A[0], pr.idx_gamma[0] = pta.nfourier, desc.idx_log10_A, desc.idx_gamma
+    for j, q in enumerate(procs):
+        pr.ncol[j], pr.idx_log10_A[j], pr.idx_gamma[j] = q.ncol, q.idx_log10_A, q.idx_gamma
+    keep["procs"] = pr
     return desc, keep
 
 
@@ -146,8 +160,19 @@ class NativeSampler:
             descs.append(d)
             self._keep.append(k)
         arr = (_abi.ModelDesc * len(descs))(*descs)
-        _abi.check(self.lib, self.lib.gst_model_set_batch(self.ctx, arr, len(descs)),
-                   "gst_model_set_batch")
+        # several power-law processes (DM, chromatic): one layout shared by the batch
+        layouts = [tuple(bytes(k["procs"])) for k in self._keep]
+        if any(v != layouts[0] for v in layouts):
+            raise ValueError("the datasets of a batch must share the power-law processes")
+        self.procs = self._keep[0]["procs"]
+        if self.procs.nproc > 1:
+            if not hasattr(self.lib, "gst_model_set_procs"):
+                raise _abi.GstNativeError("this libgst.so lacks gst_model_set_procs; rebuild")
+            _abi.check(self.lib, self.lib.gst_model_set_procs(self.ctx, arr, ct.byref(self.procs),
+                                                              len(descs)), "gst_model_set_procs")
+        else:
+            _abi.check(self.lib, self.lib.gst_model_set_batch(self.ctx, arr, len(descs)),
+                       "gst_model_set_batch")
         nd, nmax, stride = ct.c_int(), ct.c_int(), ct.c_int()
         _abi.check(self.lib, self.lib.gst_model_info(self.ctx, ct.byref(nd), ct.byref(nmax),
                                                      ct.byref(stride)), "gst_model_info")

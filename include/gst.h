@@ -113,6 +113,33 @@ typedef struct gst_model_desc {
   const int* ecorr_backend;/* n_ecorr: backend of each ECORR column */
 } gst_model_desc;
 
+/* Power-law processes of the Fourier block (additive to ABI 7: callers find
+ * gst_model_set_procs by symbol lookup).  Beside the achromatic red noise a multi-frequency
+ * analysis carries dispersion-measure variations, a second power law whose basis scales as
+ * nu^-2, and often a nu^-4 scattering process (enterprise: s = ef + eq + rn + dm + tm + ec; the
+ * reference sampler treats every log10_A / gamma parameter as hyper, gibbs.py:64-69).  The
+ * Fourier block of T is then [red | dm | chrom]: process p owns ncol[p] contiguous columns,
+ * in this order, with its own log10_A / gamma parameters and its own frequency ladder --
+ * ffreqs holds each process's repeat(f, 2) one after the other, and df restarts at each
+ * process's first pair (df_1 = f_1 - 0).  The chromatic weights (1400 MHz / nu_t)^chi are
+ * part of T: nothing past the prior phi looks at what a Fourier column means.
+ *   phi_k = A_p^2 / (12 pi^2) fyr^(gamma_p - 3) f_k^-gamma_p df_k      (column k of process p)
+ *   log|phi| = sum_p (ncol_p lc_p - gamma_p sum log f + sum log df) + timing model + ECORR
+ * One gst_model_procs is shared by the batch and is part of the structure its datasets must
+ * agree in.  Every ncol is even and positive, their sum is nfourier, every index is one of
+ * hyper_idx, and idx_log10_A[0] / idx_gamma[0] equal the descriptor's idx_log10_A / idx_gamma.
+ * Routing: such models have nparams >= 5, so they run on the persistent kernel's general
+ * (GEN) instances -- up to 8 parameters, 60 Fourier + ECORR columns -- or on the large path,
+ * where every hyper kernel takes them (lg_hyper_reg, lg_hyper<0/1/2>, lg_hyper_ecr): a model
+ * that routes somewhere with one process routes to the same kernel with two or three. */
+#define GST_NPROC_MAX 3
+typedef struct gst_model_procs {
+  int nproc;            /* 1..3 power-law processes in the Fourier block */
+  int ncol[3];          /* Fourier columns of each, in basis order; sum = nfourier */
+  int idx_log10_A[3];   /* parameter indices; [0] must equal the descriptor's */
+  int idx_gamma[3];
+} gst_model_procs;
+
 /* Per-chain state, device pointers, chain-major.  x[C*P], b[C*m], z/alpha/pout[C*nmax]
  * (nmax = largest n of the model's datasets; TOAs t >= n of a chain's dataset are never
  * touched), theta/nu[C]; status[C] may be NULL, else flags are OR-ed into it:
@@ -234,6 +261,11 @@ int gst_model_set(void* ctx, const gst_model_desc* desc);
  * dataset (its Gram and T b kernels stage one dataset's T per group); a chain whose group
  * mixes datasets is flagged with status & 8 (bit 3). */
 int gst_model_set_batch(void* ctx, const gst_model_desc* descs, int ndatasets);
+
+/* gst_model_set_batch for a Fourier block of several power-law processes (gst_model_procs
+ * above; *procs is copied).  procs NULL or nproc = 1 is gst_model_set_batch itself. */
+int gst_model_set_procs(void* ctx, const gst_model_desc* descs,
+                        const gst_model_procs* procs, int ndatasets);
 
 /* Number of datasets, largest n (row stride of per-TOA state/records) and tape stride. */
 int gst_model_info(void* ctx, int* ndatasets, int* nmax, int* tape_stride);

@@ -526,8 +526,79 @@ def wide(niter=12):
               file=sys.stderr)
 
 
+# DM and chromatic power-law processes beside the red noise (PTA(dm_gp=, chrom_gp=)): every
+# dataset has band_mhz = linspace(1150, 1850, nsub) and an injected DM realisation at MGP_DM
+MGP_DM = (-13.3, 2.8)    # injected dm_gp log10_A, gamma
+MGP_CHROM = (-14.5, 3.5)  # dm3's starting point for the (not injected) chromatic process
+MGP_DATASETS = ("dmg", "dme", "dmw", "dm3", "dmx")
+
+
+def multi_gp_model(tag):
+    """(psr, pta, x0) of one multi-process dataset; x0: the injected values, by name.
+
+    * ``dmg``: multiband(60, 3) as one backend, red 7 + DM 5 components: 24 hyper columns, the
+      process boundary at column 14 (persistent GEN instances);
+    * ``dme``: ``small_ecorr``'s pulsar with ``ecb``'s per-backend equad / ECORR and a constant
+      efac (P = 8, the GEN instances' limit), red 5 + DM 5: 20 Fourier + 24 ECORR columns;
+    * ``dmw``: ``mid``'s pulsar (390 TOAs), red 30 + DM 20: 100 columns, the boundary at column
+      60 inside the first 64 lanes (large path, lg_hyper_reg<16>);
+    * ``dm3``: the same pulsar, red 30 + DM 25 + chromatic 10: 130 columns (lg_hyper<0>);
+    * ``dmx``: ``mb``'s pulsar and model, red 10 + DM 10: 40 Fourier + 60 ECORR columns (large
+      path, ECORR epochs first: lg_hyper_ecr)."""
+    gp = lambda nc: dict(components=nc)  # noqa: E731
+    band = lambda nsub: np.linspace(1150.0, 1850.0, nsub)  # noqa: E731
+    x0 = {"dm_gp_log10_A": MGP_DM[0], "dm_gp_gamma": MGP_DM[1], "log10_A": -14.0, "gamma": 4.33,
+          "chrom_gp_log10_A": MGP_CHROM[0], "chrom_gp_gamma": MGP_CHROM[1],
+          "log10_equad": -6.8, "ASP_log10_equad": -6.6, "GUPPI_log10_equad": -7.0,
+          "ASP_log10_ecorr": -6.5, "GUPPI_log10_ecorr": -6.8, "ASP_efac": 1.1, "GUPPI_efac": 0.9}
+    if tag == "dmg":
+        psr = gdata.multiband(60, 3, seed=1644, band_mhz=band(3), dm=MGP_DM + (5,))
+        pta = PTA(psr, components=7, dm_gp=gp(5))
+    elif tag == "dme":
+        psr = gdata.multiband(nepochs=24, nsub=3, seed=2443, band_mhz=band(3), dm=MGP_DM + (5,))
+        pta = PTA(psr, components=5, selection="backend", log10_ecorr=(-8.5, -5.0), dm_gp=gp(5))
+    elif tag in ("dmw", "dm3"):
+        psr = gdata.multiband(nepochs=130, nsub=3, seed=390, band_mhz=band(3),
+                              dm=MGP_DM + (20,))
+        pta = PTA(psr, dm_gp=gp(20)) if tag == "dmw" else \
+            PTA(psr, dm_gp=gp(25), chrom_gp=gp(10))
+    elif tag == "dmx":
+        psr = gdata.multiband(band_mhz=band(3), dm=MGP_DM + (10,))
+        pta = PTA(psr, components=10, efac=(0.2, 10.0), selection="backend",
+                  log10_ecorr=(-8.5, -5.0), dm_gp=gp(10))
+    else:
+        raise ValueError(tag)
+    pre = psr.name + "_"
+    return psr, pta, [x0[nm[len(pre):]] for nm in pta.param_names]
+
+
+def multi_gp(only=None):
+    """``mgp_<ds>_dataset.npz`` and ``mgp_ref_<ds>_beta_{fixed,prior}.npz``: 12 recorded sweeps
+    (dm3: 6) of the reference from the injected values and from a prior draw.  (Not
+    ``ref_*.npz``: golden_io.fixture_names globs that pattern; tests/mgp_io.py loads these.)"""
+    for j, tag in enumerate(MGP_DATASETS):
+        if only and tag not in only:
+            continue
+        psr, pta, x0 = multi_gp_model(tag)
+        arrs = dataset_arrays(pta, psr)
+        arrs.update(freqs=psr.freqs, proc_names=np.array([q.name for q in pta.procs]),
+                    proc_components=np.array([q.components for q in pta.procs]))
+        np.savez_compressed(os.path.join(OUTDIR, f"mgp_{tag}_dataset.npz"), **arrs)
+        for k, (kind, start) in enumerate((("fixed", x0), ("prior", None))):
+            out = run_one(pta, "beta", MODELS["beta"], seed=9500 + 10 * j + k,
+                          niter=6 if tag == "dm3" else 12, x0=start)
+            out["model_kw"] = np.array(repr(MODELS["beta"]))
+            np.savez_compressed(os.path.join(OUTDIR, f"mgp_ref_{tag}_beta_{kind}.npz"), **out)
+            print(tag, kind, "P", len(x0), "n", pta.n, "m", pta.m, "procs",
+                  [(q.name, q.ncol) for q in pta.procs], "cond:", np.nanmax(out["tape_b_cond"]),
+                  file=sys.stderr)
+
+
 def main():
     os.makedirs(OUTDIR, exist_ok=True)
+    if "--only-multi-gp" in sys.argv:
+        multi_gp([a for a in sys.argv[1:] if a in MGP_DATASETS])
+        return
     if "--only-wide" in sys.argv:
         wide(12)
         return
@@ -613,6 +684,7 @@ def main():
     j1713_backends(niter)
     mid(niter)
     wide(niter)
+    multi_gp()
 
 
 if __name__ == "__main__":

@@ -2,7 +2,9 @@
 persistent kernel's GEN instances against the large path, same dataset and start.
 
     python tools/gen_rate.py [sweeps] [datasets]     e.g. python tools/gen_rate.py 200 ecb,ecq
-    (GR_PATHS=large: the large path only, e.g. for ebig's 150-column red-noise / ECORR block;
+    (datasets dmg, dme, dmw, dm3, dmx: the models with a DM (and chromatic) process beside the
+     red noise, tests/golden/mgp_<name>_dataset.npz; GR_CHAINS=2048: that chain count only;
+     GR_PATHS=large: the large path only, e.g. for ebig's 150-column red-noise / ECORR block;
      GR_DEBUG=epochs_lds[,...]: NativeSampler.set_debug flags;
      GR_STAGES=1: the large path's per-stage ms per sweep over S further timed sweeps)
 
@@ -22,6 +24,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from bench import CFG, initial_state  # noqa: E402
 from golden_io import load_dataset  # noqa: E402
+import mgp_io  # noqa: E402
 from gibbs_student_t_amd.native import NativeSampler  # noqa: E402
 
 
@@ -53,8 +56,8 @@ def main():
     names = (sys.argv[2] if len(sys.argv) > 2 else "ecb,ecq,jb").split(",")
     out = []
     for nm in names:
-        pta = load_dataset(dataset=nm)
-        for C in (512, 2048):
+        pta = mgp_io.load_dataset(nm) if nm in mgp_io.DATASETS else load_dataset(dataset=nm)
+        for C in [int(v) for v in os.environ.get("GR_CHAINS", "512,2048").split(",")]:
             for path in os.environ.get("GR_PATHS", "persistent,large").split(","):
                 r, ok, stages = rate(pta, path, C, S)
                 row = dict(dataset=nm, n=pta.n, m=pta.m, P=len(pta.params), chains=C, path=path,

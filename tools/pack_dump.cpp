@@ -1,10 +1,12 @@
 // Stand-alone driver of the host packer (csrc/gst_pack.h) for tests/test_pack.py:
 //   pack_dump <descriptor file> <output file>
 // The descriptor file is 16 int32 (n, m, nfourier, ntm, n_ecorr, nbackend, nparams, n_hyper,
-// n_white, ntm_pad, raug, MT, batch_disjoint, idx_log10_A, idx_gamma, 0), then doubles
+// n_white, ntm_pad, raug, MT, batch_disjoint, idx_log10_A, idx_gamma, nproc), then doubles
 // T[n m], residuals[n], toaerrs[n], ffreqs[nfourier], pmin[P], pmax[P], df_A[30], df_B[30],
 // then int32 backend[n], ecorr_backend[n_ecorr], ecorr_idx[nb], efac_idx[nb], equad_idx[nb],
-// hyper_idx[n_hyper], white_idx[n_white].  The output is, per buffer, a text line
+// hyper_idx[n_hyper], white_idx[n_white], and for nproc > 0 the gst_model_procs arrays
+// ncol[3], idx_log10_A[3], idx_gamma[3] (nproc = 0: the legacy packing without procs).  The
+// output is, per buffer, a text line
 // "name f8|i4 count" followed by the raw values.
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +48,13 @@ int main(int argc, char** argv) {
   const auto bk = get<int>(f, d.n), ecb = get<int>(f, d.n_ecorr), eci = get<int>(f, d.nbackend);
   const auto efi = get<int>(f, d.nbackend), eqi = get<int>(f, d.nbackend);
   const auto hi = get<int>(f, d.n_hyper), wi = get<int>(f, d.n_white);
+  gst_model_procs pr{};
+  pr.nproc = h[15];
+  if (pr.nproc > 0) {
+    const auto pv = get<int>(f, 9);
+    for (int q = 0; q < 3; ++q)
+      pr.ncol[q] = pv[q], pr.idx_log10_A[q] = pv[3 + q], pr.idx_gamma[q] = pv[6 + q];
+  }
   std::fclose(f);
   d.T = T.data(), d.residuals = r.data(), d.toaerrs = err.data(), d.ffreqs = ff.data();
   d.pmin = pmin.data(), d.pmax = pmax.data(), d.df_A = dfA.data(), d.df_B = dfB.data();
@@ -55,7 +64,8 @@ int main(int argc, char** argv) {
   d.idx_efac = efi[0], d.idx_equad = eqi[0];
   d.tm_weight = 1e40, d.efac_const = 1.0, d.mprior = 0.01, d.theta_prior_beta = 1;
 
-  const gst::PackedModel p = gst::pack_dataset(&d, h[9], h[10], h[11], h[12] != 0);
+  const gst::PackedModel p =
+      gst::pack_dataset(&d, h[9], h[10], h[11], h[12] != 0, pr.nproc > 0 ? &pr : nullptr);
   const gst::DevModel& md = p.md;
   FILE* o = std::fopen(argv[2], "wb");
   if (!o) return 2;
@@ -70,5 +80,15 @@ int main(int argc, char** argv) {
   put(o, "ints", std::vector<int>{md.nks, md.npad, md.mp, md.gx_nt, md.nkse, md.neblk, md.ncls,
                                   md.ec_disjoint, md.n, md.m, md.nf, md.ntm, md.ntm_pad, md.raug,
                                   md.nslot_toa, md.nec, md.nb});
+  // the spectrum pieces, process by process
+  put(o, "lfreq", p.lfreq), put(o, "ldf", p.ldf);
+  put(o, "sums", std::vector<double>{md.sum_lfreq, md.sum_ldf});
+  put(o, "psum_lfreq", std::vector<double>(md.psum_lfreq, md.psum_lfreq + gst::NPROC_MAX));
+  put(o, "psum_ldf", std::vector<double>(md.psum_ldf, md.psum_ldf + gst::NPROC_MAX));
+  put(o, "nproc", std::vector<int>{md.nproc});
+  put(o, "pcol", std::vector<int>(md.pcol, md.pcol + gst::NPROC_MAX + 1));
+  put(o, "pidxA", std::vector<int>(md.pidxA, md.pidxA + gst::NPROC_MAX));
+  put(o, "pidxG", std::vector<int>(md.pidxG, md.pidxG + gst::NPROC_MAX));
+  put(o, "idx_red", std::vector<int>{md.idx_logA, md.idx_gamma});
   return std::fclose(o) ? 1 : 0;
 }

@@ -10,8 +10,9 @@ starts -- must pass two-sample tests whatever the mixing.  This runs the REFEREN
 draws (``np.random.default_rng([SEED, c])``) and gibbs.py:29-51's latent start, S sweeps
 each, and keeps every THIN-th record of x, theta and nu (``Gibbs.sample`` records the state
 at the start of each sweep, gibbs.py:355-361).  Only the ``.npz`` of draws is committed
-(tests/golden/samestart_<dataset>_<model>.npz); tests/test_gpu_ks.py runs the GPU chains
-from the same starts.
+(tests/golden/samestart_<dataset>_<model>.npz, or mgp_samestart_... for the datasets with DM /
+chromatic processes); tests/test_gpu_ks.py and tests/test_gpu_mgp_law.py run the GPU chains from
+the same starts.
 
     python tools/same_start_ref.py DATASET MODEL CHAINS SWEEPS [THIN] [NPROC]
 """
@@ -31,6 +32,18 @@ OUT = os.path.join(ROOT, "tests", "golden")
 SEED = 424242
 
 
+def load_model(dataset):
+    """(pta, fixture prefix): the golden datasets, and the multi-process ones (red noise + DM
+    (+ chromatic), tests/mgp_io.py), whose fixtures are named mgp_samestart_*."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mgp_io
+    if dataset in mgp_io.DATASETS:
+        return mgp_io.load_dataset(dataset), "mgp_samestart"
+    from golden_io import load_dataset
+    return load_dataset(dataset=dataset), "samestart"
+
+
 def start(pta, c):
     lo = np.array([p.pmin for p in pta.params])
     hi = np.array([p.pmax for p in pta.params])
@@ -43,11 +56,10 @@ def worker(dataset, model, c0, c1, sweeps, thin, path):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import gibbs as refgibbs  # the reference
-    from golden_io import load_dataset
     from gibbs_student_t_amd.run_sims import MODELS
     refgibbs.map = lambda f, *a: list(builtins.map(f, *a))
     warnings.filterwarnings("ignore")
-    pta = load_dataset(dataset=dataset)
+    pta = load_model(dataset)[0]
     xs, th, nu = [], [], []
     for c in range(c0, c1):
         np.random.seed(SEED + c)
@@ -78,17 +90,14 @@ def main():
     for p in procs:
         assert p.wait() == 0
     parts = [np.load(t) for t in tmp]
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from golden_io import load_dataset
-    pta = load_dataset(dataset=dataset)
+    pta, prefix = load_model(dataset)
     out = dict(x=np.concatenate([p["x"] for p in parts]),
                theta=np.concatenate([p["theta"] for p in parts]),
                nu=np.concatenate([p["nu"] for p in parts]),
                x0=np.stack([start(pta, c) for c in range(chains)]),
                names=np.array(pta.param_names), seed=SEED, sweeps=sweeps, thin=thin,
                model=model, dataset=dataset, secs=time.time() - t0)
-    np.savez_compressed(os.path.join(OUT, f"samestart_{dataset}_{model}.npz"), **out)
+    np.savez_compressed(os.path.join(OUT, f"{prefix}_{dataset}_{model}.npz"), **out)
     for t in tmp:
         os.remove(t)
     print({k: v.shape for k, v in out.items() if hasattr(v, "shape")}, f"{time.time() - t0:.0f} s")
