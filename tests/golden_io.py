@@ -17,34 +17,63 @@ DATASETS = ("sim", "twob", "simclean", "scaled", "c3", "c4t", "c20", "tm22", "mb
 
 CHAIN_KEYS = ("chain", "bchain", "zchain", "poutchain", "thetachain", "alphachain", "dfchain")
 
+# The models with several power-law processes (red noise + DM (+ chromatic), ``PTA(dm_gp=,
+# chrom_gp=)``): ``mgp_<ds>_dataset.npz``, ``mgp_ref_<ds>_beta_{fixed,prior}.npz`` and
+# ``mgp_samestart_<ds>_beta.npz``, made by tools/gen_golden.py ``multi_gp`` and
+# tools/same_start_ref.py.  They do not match ``ref_*.npz``, so fixture_names() leaves them out.
+# dataset -> (Fourier columns of each process, ECORR columns, the path it is expected on)
+MGP_DATASETS = {
+    "dmg": ((14, 10), 0, "persistent"),
+    "dme": ((10, 10), 24, "persistent"),
+    "dmw": ((60, 40), 0, "large"),
+    "dm3": ((60, 50, 20), 0, "large"),
+    "dmx": ((20, 20), 60, "large"),
+}
+MGP_NAMES = [f"{ds}_beta_{kind}" for ds in MGP_DATASETS for kind in ("fixed", "prior")]
+
 
 def fixture_names():
     return sorted(os.path.basename(p)[4:-4] for p in glob.glob(os.path.join(GOLDEN, "ref_*.npz")))
 
 
 def load_dataset(efac=False, dataset="j1713"):
-    fn = "j1713_dataset_efac.npz" if efac else f"{dataset}_dataset.npz"
+    mgp = dataset in MGP_DATASETS
+    fn = "j1713_dataset_efac.npz" if efac else f"{'mgp_' if mgp else ''}{dataset}_dataset.npz"
     d = np.load(os.path.join(GOLDEN, fn), allow_pickle=False)
+    kw = {}
+    if "proc_names" in d.files:   # several power-law processes (tools/gen_golden.py multi_gp)
+        comps = dict(zip((str(v) for v in d["proc_names"]),
+                         (int(v) for v in d["proc_components"])))
+        kw = {k: dict(components=comps[k]) for k in ("dm_gp", "chrom_gp") if k in comps}
     if "backends" in d.files:     # general white-noise model (tools/gen_golden.py general)
-        name = str(d["names"][0]).split("_")[0]
-        return PTA.from_arrays(name, d["residuals"], d["toaerrs"], d["T"], d["Ffreqs"],
-                               int(d["components"]), float(d["tm_weight"]),
-                               efac=(0.2, 10.0) if int(d["efac_varied"]) else 1.0,
-                               backends=d["backends"], selection=str(d["selection"]),
-                               n_ecorr=int(d["n_ecorr"]), ecorr_backend=d["ecorr_backend"],
-                               log10_ecorr=tuple(d["log10_ecorr"]) or None)
-    return PTA.from_arrays("J1713+0747", d["residuals"], d["toaerrs"], d["T"], d["Ffreqs"],
-                           int(d["components"]), float(d["tm_weight"]),
-                           efac=(0.2, 10.0) if efac else 1.0)
+        kw.update(backends=d["backends"], selection=str(d["selection"]),
+                  n_ecorr=int(d["n_ecorr"]), ecorr_backend=d["ecorr_backend"],
+                  log10_ecorr=tuple(d["log10_ecorr"]) or None)
+        efac = (0.2, 10.0) if int(d["efac_varied"]) else 1.0
+    else:
+        efac = (0.2, 10.0) if efac else 1.0
+    name = str(d["names"][0]).split("_")[0] if kw else "J1713+0747"
+    pta = PTA.from_arrays(name, d["residuals"], d["toaerrs"], d["T"], d["Ffreqs"],
+                          int(d["components"]), float(d["tm_weight"]), efac=efac, **kw)
+    if mgp:
+        assert pta.param_names == [str(v) for v in d["names"]]
+    return pta
 
 
 def load_ref(name):
-    d = dict(np.load(os.path.join(GOLDEN, f"ref_{name}.npz"), allow_pickle=False))
+    """``ref_<name>.npz``, or ``mgp_ref_<name>.npz`` for a name of ``MGP_NAMES``."""
+    ds = name.split("_")[0]
+    fn = f"mgp_ref_{name}.npz" if ds in MGP_DATASETS else f"ref_{name}.npz"
+    d = dict(np.load(os.path.join(GOLDEN, fn), allow_pickle=False))
     d["kw"] = ast.literal_eval(str(d.pop("model_kw")))
     d["tape"] = {k[5:]: v for k, v in d.items() if k.startswith("tape_")}
-    ds = name.split("_")[0] if name.split("_")[0] in DATASETS else "j1713"
-    d["pta"] = load_dataset(efac="efac" in name, dataset=ds)
+    d["pta"] = load_dataset(efac="efac" in name,
+                            dataset=ds if ds in DATASETS or ds in MGP_DATASETS else "j1713")
     return d
+
+
+def load_samestart(dataset):
+    return np.load(os.path.join(GOLDEN, f"mgp_samestart_{dataset}_beta.npz"), allow_pickle=False)
 
 
 def sweep_state(ref, i):

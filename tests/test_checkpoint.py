@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from gibbs_student_t_amd.sampler import check_checkpoint, dataset_fingerprint, make_checkpoint
+from golden_io import load_dataset
 
 CFG = dict(model="mixture", tdf=4, m=0.01, vary_df=True, theta_prior="beta",
            vary_alpha=True, alpha=1e10, pspin=None, exact_bdraw=False)
@@ -53,17 +54,13 @@ def test_mismatch_is_refused(change):
 
 
 def test_equal_option_values_are_accepted():
-    """tdf = 4 vs 4.0, m = np.float64(0.01) vs 0.01: the same options (ADVICE r4)."""
+    """tdf = 4 vs 4.0, m = np.float64(0.01) vs 0.01: the same options."""
     ck = _ck()
     cfg = dict(CFG, tdf=4.0, m=np.float64(0.01), alpha=np.float64(1e10), vary_df=np.bool_(True))
     check_checkpoint(ck, cfg, (7, 5), 3, fingerprint="abc")
 
 
 def test_fingerprint_tells_datasets_apart():
-    import os
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from golden_io import load_dataset
     a, b = load_dataset(), load_dataset(dataset="c3")
     assert dataset_fingerprint(a) == dataset_fingerprint(load_dataset())
     assert dataset_fingerprint(a) != dataset_fingerprint(b)

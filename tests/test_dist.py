@@ -1,20 +1,12 @@
 """Chain sharding and the final summary all-reduce, world_size 2 over gloo (CPU)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
 from gibbs_student_t_amd import dist
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from support import free_port
 
 
 def _worker(rank, world, port, out):
@@ -32,7 +24,7 @@ def _worker(rank, world, port, out):
 def test_two_rank_summary_reduction():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -87,7 +79,7 @@ def test_two_rank_bench_workloads_partition_chains():
     keys) and agree on the data; config 4 shards the 256-dataset run_sims grid by dataset (strong scaling)."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_workload_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -120,7 +112,7 @@ def test_gather_chains_goes_to_rank0_only():
     """The chain draws are gathered to rank 0 (the only consumer), not all-gathered."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_gather_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

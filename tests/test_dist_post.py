@@ -2,23 +2,15 @@
 each rank holds the sums of its own chains; the reduced pooled vector gives every rank the
 means over all chains of all ranks."""
 import os
-import socket
 
 import numpy as np
 import torch.multiprocessing as mp
 
 from gibbs_student_t_amd import dist
 from gibbs_student_t_amd.post import PosteriorSums
+from support import free_port
 
 C, S, N, M = 3, 40, 6, 4
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _rank_chains(rank):
@@ -50,7 +42,7 @@ def _worker(rank, world, port, out):
 def test_two_rank_posterior_pooling():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -12,7 +12,7 @@ import scipy.stats
 import draw_laws as dl
 from oracle import philox_variates as pv
 from oracle.gibbs_oracle import DF_GRID, MH_PROBS, Oracle, OutlierModel
-from test_philox import KAT
+from support import KAT
 
 
 class NumpyVariates:

@@ -8,17 +8,13 @@ real-valued ones agree to a relative error (host libm and numpy differ in the la
 exp / log / cos).  The z, alpha, theta and nu laws are not covered here: they are not in
 gst_draws.h (each kernel keeps its copy; tests/test_gpu_draw_laws.py pins them per kernel).
 """
-import os
-import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from oracle import philox_variates as pv  # noqa: E402
+from oracle import philox_variates as pv
+from support import host_tool
 
 SEED = 0x5EED0123456789AB
 C, S = 3, 4                     # chains x sweeps of MH variates (x 30 steps)
@@ -43,12 +39,9 @@ def rel(a, b):
 
 @pytest.fixture(scope="module")
 def laws(tmp_path_factory):
-    assert shutil.which("g++") is not None, "the host build of the laws' header needs g++"
+    exe = host_tool(tmp_path_factory, "draws_dump",
+                    flags=("-O1", "-ffp-contract=off", "-Wno-unknown-pragmas"))
     d = tmp_path_factory.mktemp("draws")
-    exe = d / "draws_dump"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-I", os.path.join(ROOT, "gibbs_student_t_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "draws_dump.cpp"), "-o", str(exe)], check=True)
     rng = np.random.RandomState(20240611)
     inp = {}
     f = np.repeat(np.arange(1, NF // 2 + 1) / (10.0 * 365.25 * 86400.0), 2)

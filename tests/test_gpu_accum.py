@@ -7,110 +7,22 @@ and accumulating must change nothing else."""
 import numpy as np
 import pytest
 
+from gpu_support import accum_run, accum_sampler, ncu, upload_tape
+from gibbs_student_t_amd import Gibbs
+from gibbs_student_t_amd.native import ACCUM_KEYS, pack_tape
+from gibbs_student_t_amd.post import PosteriorSums
 from golden_io import load_ref, sweep_state
+from support import check_accum_sums
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd.native import ACCUM_KEYS, NativeSampler  # noqa: E402
-
 REC_KEYS = ("b", "z", "alpha", "pout")
-PER_TOA = ("z_sum", "pout_sum", "alpha_sum")
-SENTINEL = -7.25
-SEED, SWEEP0 = 11, 3
 
 
-def _pad(a, width):
-    out = np.zeros(a.shape[:-1] + (width,))
-    out[..., :a.shape[-1]] = a
-    return out
-
-
-def _init(refs, per, width):
-    """The fixtures' sweep-0 states tiled over ``per`` chains each (x spread over the prior)"""
-    parts = []
-    for d, ref in enumerate(refs):
-        s0 = sweep_state(ref, 0)
-        lo = np.array([p.pmin for p in ref["pta"].params])
-        hi = np.array([p.pmax for p in ref["pta"].params])
-        parts.append(dict(
-            x=np.random.default_rng([5, d]).uniform(lo, hi, size=(per, len(lo))),
-            b=np.tile(s0["b"], (per, 1)), z=np.tile(_pad(s0["z"], width), (per, 1)),
-            alpha=np.tile(_pad(s0["alpha"], width), (per, 1)),
-            pout=np.tile(_pad(s0["pout"], width), (per, 1)),
-            theta=np.full(per, s0["theta"]), nu=np.full(per, s0["nu"])))
-    return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-
-
-def _sampler(names, per, path="auto", waves=None, poison=False):
-    refs = [load_ref(n) for n in names]
-    if len(refs) == 1:
-        ns = NativeSampler(refs[0]["pta"], refs[0]["kw"], 0, path=path)
-        ns.alloc(per)
-    else:
-        ns = NativeSampler([r["pta"] for r in refs], [r["kw"] for r in refs], 0, path=path)
-        ns.alloc(per * len(refs), dataset=np.repeat(np.arange(len(refs)), per))
-    if waves is not None:
-        ns.set_waves(waves)
-    if poison:
-        ns.set_debug(poison=True)
-    ns.set_state(**_init(refs, per, ns.n))
-    n_of = np.repeat([r["pta"].n for r in refs], per)
-    return ns, n_of
-
-
-def _run(names, per, launches, S, *, path="auto", waves=None, poison=False, every=1,
-         accum=ACCUM_KEYS, burn=5, rec_keys=REC_KEYS):
-    """``launches`` launches of S sweeps; returns (records [C, launches * S / every, ...],
-    the sums, the final state, each chain's n).  accum None: no accumulators set."""
-    ns, n_of = _sampler(names, per, path, waves, poison)
-    acc = None
-    if accum is not None:
-        acc = ns.alloc_accum(accum)
-        for k, v in acc.items():
-            if k in PER_TOA:
-                for c, n in enumerate(n_of):
-                    v[c, n:] = SENTINEL       # entries t >= n must stay untouched
-        ns.set_accum(acc, from_sweep=SWEEP0 + burn)
-    recs = []
-    for i in range(launches):
-        rec = ns.alloc_records((S + every - 1) // every, rec_keys)
-        ns.sweep(S, records=rec, record_every=every, seed=SEED, sweep0=SWEEP0 + i * S)
-        recs.append({k: v.cpu().numpy() for k, v in rec.items()})
-    state = ns.get_state()
-    sums = None if acc is None else {k: v.cpu().numpy() for k, v in acc.items()}
-    ns.close()
-    return ({k: np.concatenate([r[k] for r in recs], axis=1) for k in rec_keys}, sums, state,
-            n_of)
-
-
-def _check_sums(rec, sums, n_of, burn, keys=ACCUM_KEYS):
-    """The sums against a sequential host sum of the records from record ``burn`` on"""
-    nrec = rec["b"].shape[1] if "b" in rec else rec["pout"].shape[1]
-    for key, rk in (("z_sum", "z"), ("pout_sum", "pout"), ("alpha_sum", "alpha"),
-                    ("b_sum", "b")):
-        if key not in keys:
-            continue
-        want = np.zeros_like(rec[rk][:, 0])
-        for i in range(burn, nrec):        # sequential, as the kernel adds (np.sum is pairwise)
-            want = want + rec[rk][:, i]
-        if key in PER_TOA:
-            for c, n in enumerate(n_of):
-                np.testing.assert_array_equal(sums[key][c, :n], want[c, :n], err_msg=f"{key} {c}")
-                assert np.all(sums[key][c, n:] == SENTINEL), f"{key}: chain {c} wrote t >= n"
-        else:
-            np.testing.assert_array_equal(sums[key], want, err_msg=key)
-    if "b_sq" in keys:
-        want = np.zeros_like(rec["b"][:, 0])
-        for i in range(burn, nrec):
-            want = want + rec["b"][:, i] * rec["b"][:, i]
-        # non-negative terms, fused or unfused multiply-add: one rounding per term
-        np.testing.assert_allclose(sums["b_sq"], want, rtol=1e-14, atol=0.0)
-    if "count" in keys:
-        np.testing.assert_array_equal(sums["count"], nrec - burn)
+def _run(*args, **kw):
+    """gpu_support.accum_run as the tuple (records, sums, final state, each chain's n)"""
+    out = accum_run(*args, **kw)
+    return out["rec"], out["sums"], out["state"], out["n_of"]
 
 
 # each case: the smallest shape that reaches one code path
@@ -138,7 +50,7 @@ def test_sums_equal_recorded_chains(case):
                                   waves=cfg.get("waves"))
     if case == "batch_ragged":
         assert n_of.min() < n_of.max() == rec["z"].shape[2]
-    _check_sums(rec, sums, n_of, 5)
+    check_accum_sums(rec, sums, n_of, 5)
     assert np.all(sums["count"] == 19)
 
 
@@ -146,13 +58,13 @@ def test_sums_equal_recorded_chains(case):
 def test_tape_mode_accumulates_too(path):
     """Parity launches (injected variates: the persistent kernel's tape instances) keep the
     sums like any other sampling launch"""
-    from gibbs_student_t_amd.native import pack_tape
     ref = load_ref("beta_fixed")
     S, C, burn = int(ref["niter"]), 5, 2
-    ns, n_of = _sampler(["beta_fixed"], C, path)
+    ns, _, _ = accum_sampler(["beta_fixed"], C, path)
+    n_of = np.full(C, ref["pta"].n)
     ns.set_state(x=np.tile(ref["xs"], (C, 1)))
     rows = pack_tape(ref["tape"], np.arange(S), ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(np.tile(rows, (C, 1, 1))).to(ns.tdev).contiguous()
+    tape = upload_tape(ns, np.tile(rows, (C, 1, 1)))
     acc = ns.alloc_accum()
     ns.set_accum(acc, from_sweep=burn)
     rec = ns.alloc_records(S, REC_KEYS)
@@ -160,7 +72,7 @@ def test_tape_mode_accumulates_too(path):
     sums = {k: v.cpu().numpy() for k, v in acc.items()}
     recs = {k: v.cpu().numpy() for k, v in rec.items()}
     ns.close()
-    _check_sums(recs, sums, n_of, burn)
+    check_accum_sums(recs, sums, n_of, burn)
     assert np.all(sums["count"] == S - burn) and S - burn >= 3
 
 
@@ -192,9 +104,9 @@ def test_thinned_run_has_the_same_sums(path):
 
 def test_two_chains_per_simd():
     """More chains than SIMDs: the two-chains-per-SIMD instance"""
-    C = 4 * torch.cuda.get_device_properties(0).multi_processor_count + 16
+    C = 4 * ncu() + 16
     rec, sums, _, n_of = _run(["beta_fixed"], C, 1, 6, path="persistent", burn=2)
-    _check_sums(rec, sums, n_of, 2)
+    check_accum_sums(rec, sums, n_of, 2)
     assert np.all(sums["count"] == 4)
 
 
@@ -204,12 +116,10 @@ def test_null_subsets(path):
     rec, sums, _, n_of = _run(["beta_fixed"], 8, 3, 8, path=path, accum=("pout_sum",),
                               rec_keys=("pout",))
     assert set(sums) == {"pout_sum"}
-    _check_sums(rec, sums, n_of, 5, keys=("pout_sum",))
+    check_accum_sums(rec, sums, n_of, 5, keys=("pout_sum",))
 
 
 def test_gibbs_record_subset_and_post():
-    from gibbs_student_t_amd import Gibbs
-    from gibbs_student_t_amd.post import PosteriorSums
     ref = load_ref("beta_fixed")
     s0 = sweep_state(ref, 0)
 

@@ -15,100 +15,26 @@ N additions add (N + 1) eps A^2 at most:
     |resid_sq_t - sum_i y_it^2|  <=  2 (m + 2 + N) eps  sum_i A_it^2.
 
 Neither bound is a measured number.  The new sums must change nothing else."""
+import ctypes as ct
+import functools
+
 import numpy as np
 import pytest
 
+from gpu_support import SENTINEL, accum_alloc, accum_run, accum_sampler, ncu, upload_tape
+from gibbs_student_t_amd import Gibbs, _abi, run_sims
+from gibbs_student_t_amd.native import ACCUM_KEYS, ACCUM_TOA_KEYS, pack_tape
+from gibbs_student_t_amd.post import PosteriorSums
 from golden_io import load_ref, sweep_state
+from support import check_accum_sums
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd.native import ACCUM_KEYS, ACCUM_TOA_KEYS, NativeSampler  # noqa: E402
-
 REC_KEYS = ("b", "z", "alpha", "pout")
-PER_TOA = ("z_sum", "pout_sum", "alpha_sum", "resid_sum", "resid_sq")
 THR = (0.1, 0.5, 0.9)
-SENTINEL = -7.25
-SEED, SWEEP0 = 11, 3
 EPS = np.finfo(np.float64).eps
 ALL_KEYS = ACCUM_KEYS + ACCUM_TOA_KEYS
-
-
-def _pad(a, width):
-    out = np.zeros(a.shape[:-1] + (width,))
-    out[..., :a.shape[-1]] = a
-    return out
-
-
-def _init(refs, per, width):
-    """The fixtures' sweep-0 states tiled over ``per`` chains each (x spread over the prior)"""
-    parts = []
-    for d, ref in enumerate(refs):
-        s0 = sweep_state(ref, 0)
-        lo = np.array([p.pmin for p in ref["pta"].params])
-        hi = np.array([p.pmax for p in ref["pta"].params])
-        parts.append(dict(
-            x=np.random.default_rng([5, d]).uniform(lo, hi, size=(per, len(lo))),
-            b=np.tile(s0["b"], (per, 1)), z=np.tile(_pad(s0["z"], width), (per, 1)),
-            alpha=np.tile(_pad(s0["alpha"], width), (per, 1)),
-            pout=np.tile(_pad(s0["pout"], width), (per, 1)),
-            theta=np.full(per, s0["theta"]), nu=np.full(per, s0["nu"])))
-    return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-
-
-def _sampler(names, per, path="auto", waves=None, poison=False):
-    refs = [load_ref(n) for n in names]
-    if len(refs) == 1:
-        ns = NativeSampler(refs[0]["pta"], refs[0]["kw"], 0, path=path)
-        ns.alloc(per)
-    else:
-        ns = NativeSampler([r["pta"] for r in refs], [r["kw"] for r in refs], 0, path=path)
-        ns.alloc(per * len(refs), dataset=np.repeat(np.arange(len(refs)), per))
-    if waves is not None:
-        ns.set_waves(waves)
-    if poison:
-        ns.set_debug(poison=True)
-    ns.set_state(**_init(refs, per, ns.n))
-    ds_of = np.repeat(np.arange(len(refs)), per)
-    return ns, refs, ds_of
-
-
-def _alloc(ns, n_of, keys, thr):
-    acc = ns.alloc_accum(keys, pout_thresholds=thr if "pout_gt" in keys else None)
-    for k, v in acc.items():
-        if k in PER_TOA or k == "pout_gt":
-            for c, n in enumerate(n_of):
-                v[..., c, n:] = SENTINEL       # entries t >= n must stay untouched
-    return acc
-
-
-def _run(names, per, launches, S, *, path="auto", waves=None, poison=False, every=1,
-         accum=ALL_KEYS, thr=THR, burn=5, rec_keys=REC_KEYS, with_accum=True):
-    """``launches`` launches of S sweeps; returns a dict: the records [C, launches * S / every,
-    ...], the sums, the final state, the fixtures and each chain's dataset.  accum None: no
-    accumulators set; with_accum False: gst_set_accum_toa alone."""
-    ns, refs, ds_of = _sampler(names, per, path, waves, poison)
-    n_of = np.array([refs[d]["pta"].n for d in ds_of])
-    acc = None
-    if accum is not None:
-        acc = _alloc(ns, n_of, accum, thr)
-        if with_accum:
-            ns.set_accum(acc, from_sweep=SWEEP0 + burn, pout_thresholds=thr)
-        else:
-            ns.set_accum_toa(acc, pout_thresholds=thr)
-    recs = []
-    for i in range(launches):
-        rec = ns.alloc_records((S + every - 1) // every, rec_keys)
-        ns.sweep(S, records=rec, record_every=every, seed=SEED, sweep0=SWEEP0 + i * S)
-        recs.append({k: v.cpu().numpy() for k, v in rec.items()})
-    state = ns.get_state()
-    sums = None if acc is None else {k: v.cpu().numpy() for k, v in acc.items()}
-    ns.close()
-    return dict(rec={k: np.concatenate([r[k] for r in recs], axis=1) for k in rec_keys},
-                sums=sums, state=state, refs=refs, ds_of=ds_of, n_of=n_of)
+_run = functools.partial(accum_run, accum=ALL_KEYS, thr=THR)
 
 
 def _check_counts(out, burn, thr=THR, nondegenerate=True):
@@ -161,16 +87,8 @@ def _check_resid(out, burn, keys=("resid_sum", "resid_sq")):
 
 
 def _check_old_sums(out, burn):
-    rec, sums = out["rec"], out["sums"]
-    nrec = rec["b"].shape[1]
-    for key, rk in (("z_sum", "z"), ("pout_sum", "pout"), ("alpha_sum", "alpha"), ("b_sum", "b")):
-        want = np.zeros_like(rec[rk][:, 0])
-        for i in range(burn, nrec):
-            want = want + rec[rk][:, i]
-        for c, n in enumerate(out["n_of"]):
-            w = n if key in PER_TOA else want.shape[1]
-            np.testing.assert_array_equal(sums[key][c, :w], want[c, :w], err_msg=f"{key} {c}")
-    np.testing.assert_array_equal(sums["count"], nrec - burn)
+    check_accum_sums(out["rec"], out["sums"], out["n_of"], burn,
+                     ("z_sum", "pout_sum", "alpha_sum", "b_sum", "count"))
 
 
 # each case: the smallest shape that reaches one code path (tests/test_gpu_accum.py)
@@ -214,15 +132,14 @@ def test_all_zero_counts():
 @pytest.mark.parametrize("path", ["persistent", "large"])
 def test_tape_mode(path):
     """Parity launches (injected variates: the persistent kernel's tape instances)"""
-    from gibbs_student_t_amd.native import pack_tape
     ref = load_ref("beta_fixed")
     S, C, burn = int(ref["niter"]), 5, 2
-    ns, refs, ds_of = _sampler(["beta_fixed"], C, path)
+    ns, refs, ds_of = accum_sampler(["beta_fixed"], C, path)
     n_of = np.full(C, ref["pta"].n)
     ns.set_state(x=np.tile(ref["xs"], (C, 1)))
     rows = pack_tape(ref["tape"], np.arange(S), ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(np.tile(rows, (C, 1, 1))).to(ns.tdev).contiguous()
-    acc = _alloc(ns, n_of, ALL_KEYS, THR)
+    tape = upload_tape(ns, np.tile(rows, (C, 1, 1)))
+    acc = accum_alloc(ns, n_of, ALL_KEYS, THR)
     ns.set_accum(acc, from_sweep=burn, pout_thresholds=THR)
     rec = ns.alloc_records(S, REC_KEYS)
     ns.sweep(S, records=rec, tape=tape)
@@ -238,7 +155,7 @@ def test_tape_mode(path):
 
 def test_two_chains_per_simd():
     """More chains than SIMDs: the two-chains-per-SIMD instance"""
-    C = 4 * torch.cuda.get_device_properties(0).multi_processor_count + 16
+    C = 4 * ncu() + 16
     out = _run(["beta_fixed"], C, 1, 6, path="persistent", burn=2)
     _check_counts(out, 2)
     # (the residual check on the first and last 8 chains: the host reference is long double)
@@ -309,9 +226,7 @@ def test_without_set_accum_nothing_is_written(path):
 
 
 def test_bad_thresholds_are_refused():
-    import ctypes as ct
-    from gibbs_student_t_amd import _abi
-    ns, _, _ = _sampler(["beta_fixed"], 2)
+    ns, _, _ = accum_sampler(["beta_fixed"], 2)
     for thr in ((0.5, 0.5), (0.9, 0.1), (0.0,), (1.0,), (float("nan"),)):
         a = _abi.AccumToa(len(thr), (ct.c_double * 4)(*thr), None, None, None)
         assert ns.lib.gst_set_accum_toa(ns.ctx, ct.byref(a)) != 0
@@ -326,7 +241,6 @@ def test_bad_thresholds_are_refused():
 def test_gibbs_median_rule_and_signal_band():
     """3 chains x 31 counted sweeps (93 is odd: no tie): the median rule of the device counts
     is that of a fully recorded run with the same seed, the band that of T @ bchain."""
-    from gibbs_student_t_amd import Gibbs
     ref = load_ref("beta_fixed")
     s0 = sweep_state(ref, 0)
     burn, N = 9, 31
@@ -385,8 +299,6 @@ def test_gibbs_median_rule_and_signal_band():
 def test_study_post_files(tmp_path):
     """One theta, two models, 2 chains, 40 sweeps with --post: each entry's post.npz holds the
     sums of that entry's chain files"""
-    from gibbs_student_t_amd import run_sims
-    from gibbs_student_t_amd.post import PosteriorSums
     run_sims.main(["--thetas", "0.1", "--models", "beta", "vvh17", "--chains", "2", "--niter",
                    "40", "--burn", "10", "--chunk", "16", "--outdir", str(tmp_path),
                    "--generator", "host", "--seed", "7", "--post", "--pout-thresholds", "0.2",

@@ -10,17 +10,17 @@ identical to a launch of its dataset alone.
 import numpy as np
 import pytest
 
+from gpu_support import open_sampler, torch, upload_tape
+from gibbs_student_t_amd import data
+from gibbs_student_t_amd._abi import STATUS_ERRORS
+from gibbs_student_t_amd.model import PTA
+from gibbs_student_t_amd.native import STATE_KEYS, NativeSampler, pack_tape
+from gibbs_student_t_amd.run_sims import MODELS
 from golden_io import fixture_names, load_ref, oracle_replay, sweep_state
+from support import (assert_replay_matches, batch_start_state, pad, prior_box, rel,
+                     start_state)
 
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler, pack_tape  # noqa: E402
-from test_gpu_parity import assert_replay_matches  # noqa: E402
 
 # three-parameter fixtures the single-chain replay covers (test_full_chain_replay), plus the
 # ragged no_outlier twin (n = 119 next to n = 130)
@@ -29,33 +29,26 @@ REPLAY = [n for n in fixture_names()
           and not n.startswith(("scaled", "c20", "tm22", "mb", "ec", "ebig", "jb"))]   # one basis shape per batch
 
 
-def _pad(a, nst):
-    out = np.zeros(a.shape[:-1] + (nst,))
-    out[..., :a.shape[-1]] = a
-    return out
-
-
 def test_batch_replays_every_fixture():
     assert any(n.startswith("simclean") for n in REPLAY)
     refs = [load_ref(n) for n in REPLAY]
-    ns = NativeSampler([r["pta"] for r in refs], [r["kw"] for r in refs], 0)
     C = len(refs)
-    ns.alloc(C, dataset=np.arange(C))
+    ns = open_sampler(refs, C, dataset=np.arange(C))
     nst = ns.n
     assert nst == max(r["pta"].n for r in refs) and min(r["pta"].n for r in refs) < nst
     S = int(refs[0]["niter"])
     s0 = [sweep_state(r, 0) for r in refs]
     ns.set_state(x=np.stack([r["xs"] for r in refs]), b=np.stack([s["b"] for s in s0]),
-                 z=np.stack([_pad(s["z"], nst) for s in s0]),
-                 alpha=np.stack([_pad(s["alpha"], nst) for s in s0]),
-                 pout=np.stack([_pad(s["pout"], nst) for s in s0]),
+                 z=np.stack([pad(s["z"], nst) for s in s0]),
+                 alpha=np.stack([pad(s["alpha"], nst) for s in s0]),
+                 pout=np.stack([pad(s["pout"], nst) for s in s0]),
                  theta=np.array([s["theta"] for s in s0]), nu=np.array([s["nu"] for s in s0]))
     tape = np.stack([pack_tape(r["tape"], np.arange(S), r["pta"].n, ns.m, ns.stride, nst)
                      for r in refs])
     rec = ns.alloc_records(S)
     for v in rec.values():
         v.zero_()
-    ns.sweep(S, records=rec, tape=torch.as_tensor(tape).to(ns.tdev).contiguous())
+    ns.sweep(S, records=rec, tape=upload_tape(ns, tape))
     got = {k: v.cpu().numpy() for k, v in rec.items()}
     assert np.all((ns.get_state()["status"] & STATUS_ERRORS) == 0)
     for c, (name, r) in enumerate(zip(REPLAY, refs)):
@@ -70,8 +63,8 @@ def test_batch_replays_every_fixture():
         for k, rk in (("b", "bchain"), ("alpha", "alphachain"), ("pout", "poutchain"),
                       ("theta", "thetachain")):
             g = got[k][c][..., :n] if k in ("alpha", "pout") else got[k][c]
-            rel = np.abs(g - r[rk]) / np.maximum(np.abs(r[rk]), 1e-300)
-            assert np.all(rel <= 1e-6), f"{name} {k}: max rel {rel.max():.3e}"
+            e = rel(g, r[rk])
+            assert np.all(e <= 1e-6), f"{name} {k}: max rel {e.max():.3e}"
         # TOAs beyond this dataset's n are never written
         assert np.all(got["alpha"][c][:, n:] == 0.0) if n < nst else True
 
@@ -83,27 +76,14 @@ def test_batch_equals_single_dataset_launches():
     per, S, seed = 6, 7, 4242
     C = per * len(refs)
     ds = np.repeat(np.arange(len(refs)), per)
-    big = NativeSampler([r["pta"] for r in refs], [r["kw"] for r in refs], 0)
-    big.alloc(C, dataset=ds)
-    nst = big.n
-
-    def init(r, k, width):
-        s = sweep_state(r, 0)
-        return dict(x=np.tile(r["xs"], (k, 1)), b=np.tile(s["b"], (k, 1)),
-                    z=np.tile(_pad(s["z"], width), (k, 1)),
-                    alpha=np.tile(_pad(s["alpha"], width), (k, 1)),
-                    pout=np.tile(_pad(s["pout"], width), (k, 1)),
-                    theta=np.full(k, s["theta"]), nu=np.full(k, s["nu"]))
-
-    parts = [init(r, per, nst) for r in refs]
-    big.set_state(**{k: np.concatenate([p[k] for p in parts]) for k in parts[0]})
+    big = open_sampler(refs, C, dataset=ds)
+    big.set_state(**batch_start_state(refs, per, big.n))
     big.sweep(S, seed=seed, sweep0=3)
     full = big.get_state()
     assert np.all((full["status"] & STATUS_ERRORS) == 0)
     for d, r in enumerate(refs):
-        one = NativeSampler(r["pta"], r["kw"], 0)
-        one.alloc(per)
-        one.set_state(**init(r, per, r["pta"].n))
+        one = open_sampler(r, per)
+        one.set_state(**start_state(r, per))
         one.sweep(S, seed=seed, sweep0=3, chain0=d * per)
         o = one.get_state()
         sl = slice(d * per, (d + 1) * per)
@@ -136,9 +116,6 @@ def test_bad_dataset_index_is_flagged():
 def test_large_path_dataset_batch_equals_single_launches():
     """The large-model path batches datasets too (ragged n, 16-chain groups per dataset):
     each chain of a 2-dataset batch is bitwise its dataset's standalone launch."""
-    from gibbs_student_t_amd import data
-    from gibbs_student_t_amd.model import PTA
-    from gibbs_student_t_amd.run_sims import MODELS
     ptas = [PTA(data.scaled_synthetic(n=n, components=40, ntm=100, seed=sd), components=40)
             for n, sd in ((1500, 11), (1333, 12))]
     cfgs = [MODELS["beta"], MODELS["t"]]
@@ -151,8 +128,7 @@ def test_large_path_dataset_batch_equals_single_launches():
     nst = big.n
 
     def init(pta, c0, width):
-        lo = np.array([p.pmin for p in pta.params])
-        hi = np.array([p.pmax for p in pta.params])
+        lo, hi = prior_box(pta)
         x = np.stack([np.random.default_rng([3, c0 + c]).uniform(lo, hi) for c in range(per)])
         z = np.zeros((per, width))
         z[:, :pta.n] = 1.0
@@ -183,19 +159,15 @@ def test_large_path_chains_do_not_depend_on_batch_partners():
     """A dataset's chains on the large path are bitwise the same launched alone or batched
     with datasets of other kernel classes: n <= 8k (one-wave white pass), 8k < n <= 32k (256
     threads) and n > 32k TOAs (1024 threads), per-TOA block sizes and hyper kernels being
-    chosen per dataset, not from the batch (VERDICT r4 weak #7; run_sims.py:80-113 runs each
+    chosen per dataset, not from the batch (run_sims.py:80-113 runs each
     dataset as an independent Gibbs object)."""
-    from gibbs_student_t_amd import data
-    from gibbs_student_t_amd.model import PTA
-    from gibbs_student_t_amd.run_sims import MODELS
     ptas = [PTA(data.scaled_synthetic(n=n, components=30, ntm=14, seed=sd), components=30)
             for n, sd in ((1000, 21), (9000, 22), (33000, 23))]
     cfg = MODELS["beta"]
     per, S, seed = 16, 3, 5
 
     def init(pta, c0, width):
-        lo = np.array([p.pmin for p in pta.params])
-        hi = np.array([p.pmax for p in pta.params])
+        lo, hi = prior_box(pta)
         x = np.stack([np.random.default_rng([7, c0 + c]).uniform(lo, hi) for c in range(per)])
         z = np.zeros((per, width))
         z[:, :pta.n] = 1.0
@@ -243,18 +215,12 @@ def test_general_white_noise_batch_matches_single_datasets():
     per, S, seed = 24, 6, 9
 
     def init(ref, c0):
-        pta = ref["pta"]
-        lo = np.array([p.pmin for p in pta.params])
-        hi = np.array([p.pmax for p in pta.params])
-        s0 = sweep_state(ref, 0)
-        return dict(x=np.stack([np.random.default_rng([11, c0 + c]).uniform(lo, hi)
-                                for c in range(per)]),
-                    b=np.tile(s0["b"], (per, 1)), z=np.tile(s0["z"], (per, 1)),
-                    alpha=np.tile(s0["alpha"], (per, 1)), pout=np.tile(s0["pout"], (per, 1)),
-                    theta=np.full(per, s0["theta"]), nu=np.full(per, s0["nu"]))
+        lo, hi = prior_box(ref["pta"])
+        return dict(start_state(ref, per),
+                    x=np.stack([np.random.default_rng([11, c0 + c]).uniform(lo, hi)
+                                for c in range(per)]))
 
-    big = NativeSampler([r["pta"] for r in refs], [r["kw"] for r in refs], 0, path="persistent")
-    big.alloc(2 * per, dataset=np.repeat(np.arange(2), per))
+    big = open_sampler(refs, 2 * per, "persistent", dataset=np.repeat(np.arange(2), per))
     parts = [init(r, j * per) for j, r in enumerate(refs)]
     big.set_state(**{k: np.concatenate([p[k] for p in parts]) for k in parts[0]})
     big.sweep(S, seed=seed, sweep0=3)
@@ -262,12 +228,11 @@ def test_general_white_noise_batch_matches_single_datasets():
     big.close()
     assert np.all((full["status"] & STATUS_ERRORS) == 0)
     for j, ref in enumerate(refs):
-        one = NativeSampler(ref["pta"], ref["kw"], 0, path="persistent")
-        one.alloc(per)
+        one = open_sampler(ref, per, "persistent")
         one.set_state(**parts[j])
         one.sweep(S, seed=seed, sweep0=3, chain0=j * per)
         alone = one.get_state()
         one.close()
         sl = slice(j * per, (j + 1) * per)
-        for k in ("x", "b", "z", "alpha", "pout", "theta", "nu", "status"):
+        for k in STATE_KEYS + ("status",):
             np.testing.assert_array_equal(full[k][sl], alone[k], err_msg=f"dataset {j} {k}")

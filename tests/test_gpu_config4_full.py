@@ -1,5 +1,5 @@
 """BASELINE config 4 at its full size on one GPU: the run_sims.py grid of 256 simulated
-datasets x 64 chains = 16384 chains in one ragged batch (VERDICT round 2, item 4).
+datasets x 64 chains = 16384 chains in one ragged batch.
 
 Property checks (no oracle at this size): every chain's status is clean, every state value
 is finite, x stays in its prior box (gibbs.py:337-339 rejects everything outside), theta in
@@ -9,15 +9,13 @@ Philox keyed by global chain id)."""
 import numpy as np
 import pytest
 
+import gpu_support  # noqa: F401  (importing it is the device gate)
+import bench
+from gibbs_student_t_amd._abi import STATUS_ERRORS
+from gibbs_student_t_amd.native import NativeSampler
+from support import prior_box
+
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-import bench  # noqa: E402
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler  # noqa: E402
 
 S, SEED = 40, 404
 
@@ -41,8 +39,7 @@ def test_config4_full_grid_properties_and_shard_split():
         assert np.all(np.isfinite(full[k])), k
     for d, (pta, cfg) in enumerate(zip(wl["ptas"], wl["cfgs"])):
         sel = wl["ds"] == d
-        lo = np.array([p.pmin for p in pta.params])
-        hi = np.array([p.pmax for p in pta.params])
+        lo, hi = prior_box(pta)
         x = full["x"][sel]
         assert np.all((x >= lo) & (x <= hi)), d
         z = full["z"][sel][:, :pta.n]

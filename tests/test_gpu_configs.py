@@ -16,16 +16,14 @@ properties that do not depend on the chain count:
 import numpy as np
 import pytest
 
+import gpu_support  # noqa: F401  (importing it is the device gate)
+from gibbs_student_t_amd._abi import STATUS_ERRORS
+from gibbs_student_t_amd import data, run_sims
+from gibbs_student_t_amd.model import PTA
+from gibbs_student_t_amd.native import NativeSampler
+from support import prior_box
+
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
-from gibbs_student_t_amd import data, run_sims  # noqa: E402
-from gibbs_student_t_amd.model import PTA  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler  # noqa: E402
 
 BETA = run_sims.MODELS["beta"]
 BETA_M = 0.01           # Gibbs(m=0.01) default prior mean of theta (gibbs.py:9)
@@ -33,8 +31,7 @@ BETA_M = 0.01           # Gibbs(m=0.01) default prior mean of theta (gibbs.py:9)
 
 def _prior_init(pta, C, c0, seed=7):
     n, m = pta.T.shape
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     x = np.stack([np.random.default_rng([seed, c0 + c]).uniform(lo, hi) for c in range(C)])
     return dict(x=x, b=np.zeros((C, m)), z=np.ones((C, n)), alpha=np.ones((C, n)),
                 pout=np.zeros((C, n)), theta=np.full(C, 0.01), nu=np.full(C, 4.0))
@@ -55,8 +52,7 @@ def test_config3_512_chains_properties():
     x = rec["x"].cpu().numpy()
     assert np.all((out["status"] & STATUS_ERRORS) == 0)
     assert np.all(np.isfinite(x)) and np.all(np.isfinite(out["b"]))
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     assert np.all((x >= lo) & (x <= hi))
     zt = psr.meta["z_true"].astype(bool)
     assert zt.sum() >= 3

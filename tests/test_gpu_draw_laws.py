@@ -17,7 +17,6 @@ The observed statistics of an MI355X run are in profiles/draw_laws.json.
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -25,20 +24,16 @@ import pytest
 import scipy.stats
 
 import draw_laws as dl
+from gpu_support import upload_tape
+from gibbs_student_t_amd import _abi
+from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR
+from gibbs_student_t_amd.native import NativeSampler
+from oracle import philox_variates as pv
+from oracle.gibbs_oracle import DF_GRID, Oracle, OutlierModel
+from support import host_tool
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd import _abi  # noqa: E402
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler  # noqa: E402
-from oracle import philox_variates as pv  # noqa: E402
-from oracle.gibbs_oracle import DF_GRID, Oracle, OutlierModel  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEBUG_BITS = {"large_hyper": _abi.DEBUG_LARGE_HYPER, "epochs_lds": _abi.DEBUG_EPOCHS_LDS}
 # seeds and counter offsets are constants: (seed, sweep0, chain0) by case parity
 SEEDS = ((0x5EED0001, 0, 0), (0x9E3779B97F4A7C15, 1_000_003, 3_000_000_019))
@@ -80,7 +75,7 @@ def launch(pta, kw, st, x, path, mask, C, S, seed, sweep0=0, chain0=0, debug=Non
     if timing:
         ns.set_timing(True)
     rec = ns.alloc_records(S, keys=keys)
-    tp = None if tape is None else torch.as_tensor(tape).to(ns.tdev).contiguous()
+    tp = None if tape is None else upload_tape(ns, tape)
     ns.sweep(S, records=rec, mask=mask, seed=seed, sweep0=sweep0, chain0=chain0, tape=tp)
     fin = ns.get_state()
     counts = {k: v[1] for k, v in ns.kernel_times().items()} if timing else {}
@@ -108,12 +103,7 @@ PERSISTENT_SHAPES = {"MT 10": "MT 10 K0 2", "MT 8": "MT 8 K0 2", "K0 3": "MT 10 
 
 @pytest.fixture(scope="module")
 def plan_bin(tmp_path_factory):
-    assert shutil.which("g++"), "the kernel check needs g++ (tools/plan_dump.cpp)"
-    out = tmp_path_factory.mktemp("plan") / "plan_dump"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "gibbs_student_t_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "plan_dump.cpp"), "-o", str(out)], check=True)
-    return str(out)
+    return host_tool(tmp_path_factory, "plan_dump", required=True)
 
 
 def planned_b_kernels(plan_bin, pta, mask, debug):

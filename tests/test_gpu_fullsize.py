@@ -14,16 +14,14 @@ import warnings
 import numpy as np
 import pytest
 
+import gpu_support  # noqa: F401  (importing it is the device gate)
+from gibbs_student_t_amd._abi import STATUS_ERRORS
+from gibbs_student_t_amd import Gibbs, data
+from gibbs_student_t_amd.model import PTA
+from oracle.gibbs_oracle import ChainState, Oracle, OutlierModel
+from support import prior_box
+
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
-from gibbs_student_t_amd import Gibbs, data  # noqa: E402
-from gibbs_student_t_amd.model import PTA  # noqa: E402
-from oracle.gibbs_oracle import ChainState, Oracle, OutlierModel  # noqa: E402
 
 KW = dict(model="mixture", vary_df=True, theta_prior="beta")   # run_sims.py:98-99
 
@@ -41,8 +39,7 @@ def test_fullsize_sampler_and_likelihoods(big):
     g = Gibbs(pta, **KW, nchains=2, seed=17)
     assert g._native.path == "large"
     rng = np.random.default_rng(3)
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     x0 = np.stack([rng.uniform(lo, hi) for _ in range(2)])
     x = g.sample(x0, niter=4)
     assert np.all((g.status & STATUS_ERRORS) == 0)
@@ -85,8 +82,7 @@ def test_largest_lds_hyper_block():
     g = Gibbs(pta, **KW, nchains=C, seed=23)
     assert g._native.path == "large"
     rng = np.random.default_rng(4)
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     x = g.sample(rng.uniform(lo, hi, size=(C, len(lo))), niter=2)
     assert np.all((g.status & STATUS_ERRORS) == 0)
     w, h = g.get_lnlikelihood_white(x), g.get_lnlikelihood(x)

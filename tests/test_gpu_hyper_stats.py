@@ -9,27 +9,26 @@ white-noise (8, 2, 2, 62) instance) with their narrowed hyper prior, the full-si
 J1713+0747 fixture on (10, 3, 2, 76).  Likelihoods are held to the suite's 1e-10 relative
 (tests/test_gpu_parity.py's RTOL and its long-double arbitration for ill-conditioned Sigma).
 """
+import os
+import sys
 import warnings
 
 import numpy as np
 import pytest
 
-from golden_io import load_ref, sweep_state
+from gpu_support import accum_run, open_sampler, upload_tape
+from gibbs_student_t_amd import _abi
+from gibbs_student_t_amd.native import pack_tape
+from gibbs_student_t_amd.run_sims import MODELS
+from golden_io import GOLDEN, load_dataset, load_ref, oracle_replay, sweep_state
+from oracle.gibbs_oracle import ChainState, Oracle, OutlierModel
+from support import (MIXTURE_KW as KW, RTOL, assert_lnl_within_reference_error,
+                     assert_replay_matches, check_accum_sums, narrowed_prior_model, prior_box,
+                     start_state, states_at)
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd import _abi  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler  # noqa: E402
-from oracle.gibbs_oracle import (ChainState, Oracle, OutlierModel,  # noqa: E402
-                                 lnlike_marginal_extended)
-from test_gpu_hyper_steps import KW, _model  # noqa: E402
-
 C = 64
-RTOL = 1e-10
 
 
 def _states(pta, x0, rng):
@@ -37,8 +36,7 @@ def _states(pta, x0, rng):
     tenth of the TOAs flagged as outliers with alpha = 5."""
     orc = Oracle(pta, OutlierModel(**KW))
     n, m = len(orc.r), pta.get_basis()[0].shape[1]
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     hyp = np.zeros(len(x0), bool)
     hyp[orc.hind] = True
     x = np.where(hyp[None], rng.uniform(lo, hi, size=(C, len(x0))), x0[None])
@@ -59,9 +57,7 @@ def _check_lnl(pta, orc, st, got, label):
         assert np.isfinite(want) and np.isfinite(got[c]), (label, c, want, got[c])
         if abs(got[c] - want) <= RTOL * abs(want):
             continue
-        ext, scale = lnlike_marginal_extended(pta, cs, st["x"][c], with_scale=True)
-        assert abs(got[c] - ext) <= max(2 * abs(want - ext), RTOL * scale), \
-            f"{label}[{c}]: gpu {got[c]!r} oracle {want!r} extended {ext!r} scale {scale:.3e}"
+        assert_lnl_within_reference_error(pta, cs, st["x"][c], got[c], want, f"{label}[{c}]")
 
 
 @pytest.mark.parametrize("kind", ["classic", "general"])
@@ -69,10 +65,9 @@ def test_eval_lnlike_small_instances(kind):
     """eval_only marginal likelihood of 64 states on the (8, 2, 2, 56) instance with a model
     smaller than the instance (dummy pad columns: pivot exactly 1) and on the general
     white-noise (8, 2, 2, 62) instance, against the oracle."""
-    pta, x0 = _model(kind, 0.03, 0.03)
+    pta, x0 = narrowed_prior_model(kind, 0.03, 0.03)
     orc, st = _states(pta, x0, np.random.default_rng(41))
-    ns = NativeSampler(pta, KW, 0, path="persistent")
-    ns.alloc(C)
+    ns = open_sampler(dict(pta=pta, kw=KW), C, "persistent")
     ns.set_state(**st)
     _, h = ns.eval_lnlike()
     ns.close()
@@ -85,12 +80,10 @@ def test_eval_lnlike_j1713():
     ref = load_ref("beta_fixed")
     K = 11
     idx = np.arange(C) // K
-    ss = [sweep_state(ref, i) for i in idx]
-    st = {k: np.stack([s[k] for s in ss]) for k in ("b", "z", "alpha", "pout")}
+    st, ss = states_at(ref, idx)
     st.update(x=ref["tape"]["hyper_lnl_x"].reshape(-1, len(ref["xs"]))[:C],
               theta=np.array([s["theta"] for s in ss]), nu=np.array([s["nu"] for s in ss]))
-    ns = NativeSampler(ref["pta"], ref["kw"], 0, path="persistent")
-    ns.alloc(C)
+    ns = open_sampler(ref, C, "persistent")
     ns.set_state(**st)
     _, h = ns.eval_lnlike()
     ns.close()
@@ -102,8 +95,7 @@ def test_failed_factor_is_minus_inf_and_flagged():
     -inf (gibbs.py:320-324) and a hyper block started there sets status bit 0."""
     ref = load_ref("beta_fixed")
     s0 = sweep_state(ref, 0)
-    ns = NativeSampler(ref["pta"], ref["kw"], 0, path="persistent")
-    ns.alloc(C)
+    ns = open_sampler(ref, C, "persistent")
     one = lambda v: np.tile(np.asarray(v, float), (C, 1))   # noqa: E731
     ns.set_state(x=one(ref["xs"]), b=np.zeros((C, ns.m)), z=np.ones((C, ns.n)),
                  alpha=np.full((C, ns.n), -1.0), pout=one(s0["pout"]),
@@ -119,10 +111,9 @@ def test_failed_factor_is_minus_inf_and_flagged():
 def test_posterior_sums_of_three_sweeps():
     """ACC instance: the sums over 3 sweeps are the sequential sums of the recorded chain
     (tests/test_gpu_accum.py's check, at this module's 64 chains)."""
-    from test_gpu_accum import _check_sums, _run
-    rec, sums, _, n_of = _run(["beta_fixed"], C, 1, 3, path="persistent", burn=0)
-    _check_sums(rec, sums, n_of, 0)
-    assert np.all(sums["count"] == 3)
+    out = accum_run(["beta_fixed"], C, 1, 3, path="persistent", burn=0)
+    check_accum_sums(out["rec"], out["sums"], out["n_of"], 0)
+    assert np.all(out["sums"]["count"] == 3)
 
 
 def test_last_step_accept_and_reject_draw_b():
@@ -132,28 +123,20 @@ def test_last_step_accept_and_reject_draw_b():
     refactors at x for it); 32 chains each.  Both against the oracle replaying the same tapes
     (tests/test_gpu_parity.py's tolerances), and the rejected side's b bitwise that of a launch
     with the direct update_b mask from the same x."""
-    from golden_io import oracle_replay
-    from gibbs_student_t_amd.native import pack_tape
-    from test_gpu_parity import assert_replay_matches
     ref = load_ref("beta_fixed")
-    s0 = sweep_state(ref, 0)
     refs = []
     for u in (1e-300, 1e300):
         r = dict(ref)
         r["tape"] = {k: np.array(v, copy=True) for k, v in ref["tape"].items()}
         r["tape"]["hyper_acc"][0][9] = u
         refs.append(r)
-    ns = NativeSampler(ref["pta"], ref["kw"], 0, path="persistent")
-    ns.alloc(C)
-    one = lambda v: np.tile(np.asarray(v, float), (C, 1))   # noqa: E731
-    start = dict(b=one(s0["b"]), z=one(s0["z"]), alpha=one(s0["alpha"]), pout=one(s0["pout"]),
-                 theta=np.full(C, s0["theta"]), nu=np.full(C, s0["nu"]))
-    ns.set_state(x=one(ref["xs"]), **start)
+    ns = open_sampler(ref, C, "persistent")
+    start = start_state(ref, C)
+    ns.set_state(**start)
     rows = np.stack([pack_tape(refs[c >= C // 2]["tape"], [0, 1], ns.n, ns.m, ns.stride)
                      for c in range(C)])
-    tape = torch.as_tensor(rows).to(ns.tdev).contiguous()
     rec = ns.alloc_records(2)
-    ns.sweep(2, records=rec, tape=tape)
+    ns.sweep(2, records=rec, tape=upload_tape(ns, rows))
     got = {k: v.cpu().numpy() for k, v in rec.items()}
     assert np.all((ns.get_state()["status"] & _abi.STATUS_ERRORS) == 0)
     want = [oracle_replay(r, 2) for r in refs]
@@ -168,9 +151,9 @@ def test_last_step_accept_and_reject_draw_b():
         np.testing.assert_array_equal(v[C // 2:], np.broadcast_to(v[C // 2], v[C // 2:].shape), k)
     # the rejected side drew b from a refactorisation at its final x: so does a launch with
     # the direct update_b mask from that x, the start state and the same draw term
-    ns.set_state(x=got["x"][:, 1], **start)
+    ns.set_state(**dict(start, x=got["x"][:, 1]))
     ns.sweep(1, mask=_abi.STAGE_B | _abi.STAGE_B_FORCE,
-             tape=torch.as_tensor(rows[:, :1]).to(ns.tdev).contiguous())
+             tape=upload_tape(ns, rows[:, :1]))
     direct = ns.get_state()["b"]
     ns.close()
     np.testing.assert_array_equal(direct[C // 2:], got["b"][C // 2:, 1])
@@ -181,13 +164,9 @@ def vvh17_floor_run():
     resolution, so the first b draw takes the SVD-floor pass), 2 sweeps with the kernel's own
     variates: the final x, b and status.  `python tests/test_gpu_hyper_stats.py OUT.npz`
     writes them (the golden was written so by the build before the step loop's rework)."""
-    from golden_io import load_dataset
-    from gibbs_student_t_amd.run_sims import MODELS
     pta = load_dataset()
-    ns = NativeSampler(pta, MODELS["vvh17"], 0, path="persistent")
-    ns.alloc(C)
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    ns = open_sampler(dict(pta=pta, kw=MODELS["vvh17"]), C, "persistent")
+    lo, hi = prior_box(pta)
     ns.set_state(x=np.random.default_rng(3).uniform(lo, hi, size=(C, len(lo))),
                  z=np.ones((C, ns.n)), alpha=np.full((C, ns.n), 1e10),
                  theta=np.full(C, 0.01), nu=np.full(C, 4.0))
@@ -200,8 +179,6 @@ def vvh17_floor_run():
 def test_vvh17_floor_draw_matches_golden():
     """The floor draw (pass 1 of the hyper block: floor_shift from the harvested pivots, then
     the refactorisation of Sigma + f I) gives the recorded status floor counts, x and b."""
-    import os
-    from golden_io import GOLDEN
     want = np.load(os.path.join(GOLDEN, "hyper_stats_vvh17.npz"))
     got = vvh17_floor_run()
     assert np.sum((want["status"] & _abi.STATUS_FLOOR) != 0) >= C // 2   # the pass is taken
@@ -210,5 +187,4 @@ def test_vvh17_floor_draw_matches_golden():
 
 
 if __name__ == "__main__":
-    import sys
     np.savez(sys.argv[1], **vvh17_floor_run())

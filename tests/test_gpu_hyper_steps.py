@@ -17,7 +17,6 @@ the tests count them again from the oracle's replay and require each to occur.
 Tolerances are tests/test_gpu_parity.py's (assert_replay_matches): x, z, theta, nu exact; b
 normwise and alpha / pout elementwise <= 1e-10 relative, the long-double mean arbitrating b.
 """
-import os
 import warnings
 from collections import Counter
 
@@ -25,42 +24,16 @@ import numpy as np
 import pytest
 import scipy.linalg as sl
 
-from golden_io import GOLDEN
-from gibbs_student_t_amd import data
-from gibbs_student_t_amd.model import PTA
+from gibbs_student_t_amd._abi import STATUS_ERRORS
+from gibbs_student_t_amd.native import STATE_KEYS, pack_tape
 from oracle.gibbs_oracle import (MH_PROBS, MH_SIZES, ChainState, Oracle, OutlierModel,
                                  TapeVariates, choice_from_uniform)
-
-KW = dict(model="mixture", vary_df=True, theta_prior="beta")
+from support import MIXTURE_KW as KW, assert_replay_matches, narrowed_prior_model, prior_box
 C, S = 16, 30
 EVENTS = ("next_out_on_accept_only", "next_out_on_reject_only", "two_consecutive_out",
           "last_in_prior_accepted", "last_in_prior_rejected", "all_ten_out")
 # (seed, half-width of the log10_A prior, of the gamma prior): found on the CPU (module doc)
 CASES = {"classic": (2, 0.03, 0.03), "general": (2, 0.03, 0.03)}
-
-
-def _model(kind, wA, wg):
-    """The model with log10_A / gamma priors of half-widths wA / wg around the start x0 (and
-    log10_ecorr priors of half-width wA in the general model)."""
-    A0, g0 = -14.0, 4.33
-    pri = dict(log10_A=(A0 - wA, A0 + wA), gamma=(g0 - wg, g0 + wg))
-    if kind == "classic":
-        pta = PTA(data.scaled_synthetic(n=100, components=10, ntm=8, seed=3), components=10,
-                  **pri)
-    else:
-        d = np.load(os.path.join(GOLDEN, "ecb_dataset.npz"), allow_pickle=False)
-        pta = PTA.from_arrays(str(d["names"][0]).split("_")[0], d["residuals"], d["toaerrs"],
-                              d["T"], d["Ffreqs"], int(d["components"]), float(d["tm_weight"]),
-                              efac=(0.2, 10.0) if int(d["efac_varied"]) else 1.0,
-                              backends=d["backends"], selection=str(d["selection"]),
-                              n_ecorr=int(d["n_ecorr"]), ecorr_backend=d["ecorr_backend"],
-                              log10_ecorr=(-6.6 - wA, -6.6 + wA), **pri)
-    x0 = []
-    for p in pta.params:
-        nm = p.name
-        x0.append(g0 if "gamma" in nm else A0 if "log10_A" in nm else 1.0 if "efac" in nm
-                  else -6.6 if "ecorr" in nm else -6.8)
-    return pta, np.array(x0)
 
 
 class _DrawnTape(TapeVariates):
@@ -145,12 +118,11 @@ def make_case(kind):
     """The model, C start points, the drawn tape ([C][S] per field), the oracle's records
     ([C][S] per key, the state at each sweep's start) and the event counts."""
     seed, wA, wg = CASES[kind]
-    pta, x0 = _model(kind, wA, wg)
+    pta, x0 = narrowed_prior_model(kind, wA, wg)
     orc = _DrawingOracle(pta, OutlierModel(**KW))
     rng = np.random.default_rng(seed)
     n, m = len(orc.r), pta.get_basis()[0].shape[1]
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     hyp = np.zeros(len(x0), bool)
     hyp[orc.hind] = True
     ev = Counter({k: 0 for k in EVENTS})
@@ -165,7 +137,7 @@ def make_case(kind):
                             pout=np.zeros(n), theta=0.05, nu=4.0)
             starts.append(dict(x=x.copy(), b=st.b.copy(), z=st.z.copy(), alpha=st.alpha.copy(),
                                pout=st.pout.copy(), theta=st.theta, nu=st.nu))
-            rec = {k: [] for k in ("x", "b", "z", "alpha", "pout", "theta", "nu")}
+            rec = {k: [] for k in STATE_KEYS}
             tp = []
             for _ in range(S):
                 for k, v in (("x", x), ("b", st.b), ("z", np.asarray(st.z, float)),
@@ -194,10 +166,9 @@ def case(kind):
 
 
 def _gpu():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():  # pragma: no cover
-        pytest.skip("needs a HIP device")
-    return torch
+    """The device gate, taken per test: this module's CPU test must run without a device."""
+    import gpu_support
+    return gpu_support
 
 
 @pytest.mark.gpu
@@ -206,21 +177,17 @@ def test_narrowed_prior_replay_matches_oracle(kind, shape):
     """16 chains x 30 sweeps in tape mode under the narrowed hyper prior: every sequencing
     event occurs in the oracle's replay, and the kernel's records are the oracle's (x, z,
     theta, nu exact; b, alpha, pout within test_gpu_parity.py's tolerances)."""
-    torch = _gpu()
-    from gibbs_student_t_amd._abi import STATUS_ERRORS
-    from gibbs_student_t_amd.native import NativeSampler, pack_tape
-    from test_gpu_parity import assert_replay_matches
+    gpu = _gpu()
     cs = case(kind)
     print(kind, dict(cs["events"]))
     for k in EVENTS:
         assert cs["events"][k] > 0, (k, dict(cs["events"]))
-    ns = NativeSampler(cs["pta"], KW, 0, path="persistent")
-    ns.alloc(C)
+    ns = gpu.open_sampler(dict(pta=cs["pta"], kw=KW), C, "persistent")
     ns.set_state(**{k: np.stack([np.asarray(s[k], float) for s in cs["starts"]])
-                    for k in ("x", "b", "z", "alpha", "pout", "theta", "nu")})
+                    for k in STATE_KEYS})
     rows = np.stack([pack_tape(t, np.arange(S), ns.n, ns.m, ns.stride) for t in cs["tapes"]])
     rec = ns.alloc_records(S)
-    ns.sweep(S, records=rec, tape=torch.as_tensor(rows).to(ns.tdev).contiguous())
+    ns.sweep(S, records=rec, tape=gpu.upload_tape(ns, rows))
     got = {k: v.cpu().numpy() for k, v in rec.items()}
     status = ns.get_state()["status"]
     ns.close()
@@ -239,15 +206,14 @@ def test_philox_launch_same_records_on_both_builds(kind):
     records and final states.  The two-chains-per-SIMD build is picked for launches of more
     chains than SIMDs, so its 64 chains are the first of such a launch (chains are keyed by
     their global index: the others do not touch them)."""
-    torch = _gpu()
-    from gibbs_student_t_amd.native import NativeSampler
+    gpu = _gpu()
     seed, wA, wg = CASES[kind]
-    pta, x0 = _model(kind, wA, wg)
+    pta, x0 = narrowed_prior_model(kind, wA, wg)
     C2, S2 = 64, 20
-    simds = 4 * torch.cuda.get_device_properties(0).multi_processor_count
+    simds = 4 * gpu.ncu()
     outs = []
     for Cl in (C2, simds + C2):
-        ns = NativeSampler(pta, KW, 0, path="persistent")
+        ns = gpu.NativeSampler(pta, KW, 0, path="persistent")
         ns.set_waves(1)
         ns.alloc(Cl)
         ns.set_state(x=np.tile(x0, (Cl, 1)), z=np.zeros((Cl, ns.n)), alpha=np.ones((Cl, ns.n)),

@@ -8,74 +8,45 @@ global scratch).  If any of it leaked from one sweep into the next, a launch of 
 would differ from S launches of one sweep each, where every sweep starts from fresh LDS and
 registers.  So: one launch of S sweeps must equal S one-sweep launches BITWISE, records
 and final state, for every build the host can pick (one chain per SIMD, two chains per
-SIMD with the fair-priority counter, two waves per chain) -- VERDICT round 2, item 1.
+SIMD with the fair-priority counter, two waves per chain).
 """
 import numpy as np
 import pytest
 
+from gpu_support import (builds, launch_records, open_sampler, single_sweep_differences,
+                         torch)
 from gibbs_student_t_amd import _abi
-
+from gibbs_student_t_amd.native import STATE_KEYS as KEYS
 from golden_io import load_ref, sweep_state
-from test_gpu_parity import _native
-from test_gpu_waves import KEYS, _init
+from support import prior_box, rel, start_state, states_at
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-
 # (+ the general white-noise instances: two backends with ECORR, one backend with ECORR,
-# J1713+0747 with two backends and no ECORR; two waves per chain for them since round 6)
+# J1713+0747 with two backends and no ECORR)
 FIXTURES = ("beta_efac_fixed", "c3_beta_fixed", "tm22_beta_fixed", "vvh17_prior",
             "ecb_beta_fixed", "ecq_t_fixed", "jb_uniform_fixed")
 
 
-def _skip_pair(name, build):
-    """(round 5: the general white-noise instances had no pair build; they have since round 6)"""
-
-
-def _ncu():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _builds():
-    # (label, chains, waves): wpb 1 / OCC 1 (C <= CUs), two waves per chain, and the
-    # two-chains-per-SIMD build (C > 4 x CUs picks OCC = 2 and the progress counter)
-    return (("occ1", 96, 1), ("pair", 96, 2), ("occ2", 4 * _ncu() + 64, 1))
+def _native(ref, C, waves=None):
+    return open_sampler(ref, C, "persistent", waves, skip_if_no_instance=True)
 
 
 @pytest.mark.parametrize("name", FIXTURES)
 @pytest.mark.parametrize("build", ("occ1", "pair", "occ2"))
 def test_one_launch_equals_single_sweep_launches(name, build):
-    _skip_pair(name, build)
-    label, C, waves = next(b for b in _builds() if b[0] == build)
+    label, (C, waves) = build, builds()[build]
     ref = load_ref(name)
     S, seed, sweep0 = 100, 11, 5
-    init = _init(ref, C, 21)
+    init = start_state(ref, C, 21)
 
-    ns = _native(ref, C, "persistent")
-    ns.set_waves(waves)
+    ns = _native(ref, C, waves)
     ns.set_state(**init)
-    rec = ns.alloc_records(S)
-    ns.sweep(S, records=rec, seed=seed, sweep0=sweep0)
-    long_state = {k: v.clone() for k, v in ns.state.items()}
-    ns.close()
+    rec, long_state = launch_records(ns, S, seed=seed, sweep0=sweep0)
 
-    ns = _native(ref, C, "persistent")
-    ns.set_waves(waves)
+    ns = _native(ref, C, waves)
     ns.set_state(**init)
-    bad = []
-    for s in range(S):
-        for k in KEYS:        # the state entering sweep s is record s of the long launch
-            if not torch.equal(ns.state[k], rec[k][:, s]):
-                bad.append((s, k))
-        if bad:
-            break
-        ns.sweep(1, seed=seed, sweep0=sweep0 + s)
-    if not bad:
-        for k in KEYS + ("status",):
-            if not torch.equal(ns.state[k], long_state[k]):
-                bad.append((S, k))
-    ns.close()
+    bad = single_sweep_differences(ns, rec, long_state, S, seed, sweep0)
     assert not bad, f"{label}: first difference (sweep, array) {bad[:4]}"
 
 
@@ -85,23 +56,17 @@ def test_poisoned_lds_and_scratch_change_nothing(name, build):
     """GST_DEBUG_POISON overwrites every chain's LDS (S0 / stage scratch, published columns,
     junk rows, MH variates, phi^-1) and its parked timing-model factor with NaN at the start
     of every sweep.  The chains must be bitwise those of an ordinary launch: no sweep reads
-    a word it did not write itself (the stale-LDS hypothesis of VERDICT round 2, item 1)."""
-    _skip_pair(name, build)
-    label, C, waves = next(b for b in _builds() if b[0] == build)
+    a word it did not write itself (the stale-LDS hypothesis)."""
+    label, (C, waves) = build, builds()[build]
     ref = load_ref(name)
     S, seed, sweep0 = 100, 12, 9
-    init = _init(ref, C, 22)
+    init = start_state(ref, C, 22)
     outs = []
     for poison in (False, True):
-        ns = _native(ref, C, "persistent")
-        ns.set_waves(waves)
+        ns = _native(ref, C, waves)
         ns.set_debug(poison=poison)
         ns.set_state(**init)
-        rec = ns.alloc_records(S)
-        ns.sweep(S, records=rec, seed=seed, sweep0=sweep0)
-        outs.append(({k: v.clone() for k, v in rec.items()},
-                     {k: v.clone() for k, v in ns.state.items()}))
-        ns.close()
+        outs.append(launch_records(ns, S, seed=seed, sweep0=sweep0))
     (r0, s0), (r1, s1) = outs
     for k in KEYS:
         assert torch.equal(r0[k], r1[k]), f"{label}: record {k} differs under poisoning"
@@ -118,32 +83,24 @@ def test_low_rank_gram_matches_mfma_gram(name):
     1e-11 relative (the Gram feeds only the marginal one), and 40 sweeps of 64 chains from
     the same Philox stream make the same MH, z and nu decisions with b, alpha, pout within
     1e-8 relative."""
-    from test_gpu_parity import _native, _rel
     ref = load_ref(name)
     S = int(ref["niter"])
-    ss = [sweep_state(ref, i) for i in range(S)]
-    init = {k: np.stack([s[k] for s in ss]) for k in ("b", "z", "alpha", "pout")}
+    init, ss = states_at(ref, range(S))
     got = []
     for mfma in (False, True):
-        ns = _native(ref, S, "persistent")
+        ns = _native(ref, S)
         ns.set_debug(mfma_gram=mfma)
         ns.set_state(x=ref["chain"][:S], theta=np.array([s["theta"] for s in ss]),
                      nu=np.array([s["nu"] for s in ss]), **init)
         got.append(ns.eval_lnlike())
         ns.close()
-    assert np.all(_rel(got[0][1], got[1][1]) <= 1e-11), _rel(got[0][1], got[1][1]).max()
+    assert np.all(rel(got[0][1], got[1][1]) <= 1e-11), rel(got[0][1], got[1][1]).max()
     np.testing.assert_array_equal(got[0][0], got[1][0])
     C, n = 64, ref["pta"].n
-    lo = np.array([p.pmin for p in ref["pta"].params])
-    hi = np.array([p.pmax for p in ref["pta"].params])
-    s0 = ss[0]
-    st0 = dict(x=np.random.default_rng(2).uniform(lo, hi, size=(C, len(lo))),
-               b=np.tile(s0["b"], (C, 1)), z=np.tile(s0["z"], (C, 1)),
-               alpha=np.tile(s0["alpha"], (C, 1)), pout=np.tile(s0["pout"], (C, 1)),
-               theta=np.full(C, s0["theta"]), nu=np.full(C, s0["nu"]))
+    st0 = start_state(ref, C, 2)
     out = []
     for mfma in (False, True):
-        ns = _native(ref, C, "persistent")
+        ns = _native(ref, C)
         ns.set_debug(mfma_gram=mfma)
         ns.set_state(**st0)
         ns.sweep(40, seed=17, sweep0=1)
@@ -154,7 +111,7 @@ def test_low_rank_gram_matches_mfma_gram(name):
         & (a["nu"] == b["nu"])
     assert same.mean() >= 0.95, same.mean()
     for k in ("b", "alpha", "pout", "theta"):
-        r = _rel(a[k][same], b[k][same])
+        r = rel(a[k][same], b[k][same])
         assert np.all(r <= 1e-8), f"{k}: {r.max():.3e}"
 
 
@@ -162,15 +119,14 @@ def test_low_rank_gram_matches_mfma_gram(name):
 def test_low_rank_gram_alpha_gate_and_path_counts(alpha, path):
     """The low-rank Gram subtracts c_k (1 - 1 / alpha_t) of a class Gram's share per flagged
     TOA, so a direction fixed by flagged TOAs alone keeps an absolute error ~eps c_k |row|^2
-    against its true size c_k |row|^2 / alpha_t (ADVICE r5).  The kernel takes it only while
+    against its true size c_k |row|^2 / alpha_t.  The kernel takes it only while
     every flagged alpha is <= 2^20.  Ten flagged TOAs of J1713 (one noise class): at alpha =
     30 the Gram runs low-rank, at 1e8 (vvh17's fixed alpha is 1e10) on the MFMA -- counted by
     gst_gram_counts over a GST_STAGE_GRAM launch -- and the likelihoods at 64 prior draws
     agree with the forced MFMA Gram to 1e-11 relative (bitwise at 1e8: the same MFMA Gram)."""
     ref = load_ref("beta_fixed")
     C, n = 64, ref["pta"].n
-    lo = np.array([p.pmin for p in ref["pta"].params])
-    hi = np.array([p.pmax for p in ref["pta"].params])
+    lo, hi = prior_box(ref["pta"])
     s0 = sweep_state(ref, 0)
     z = np.zeros((C, n))
     z[:, 7:130:13] = 1.0
@@ -180,7 +136,7 @@ def test_low_rank_gram_alpha_gate_and_path_counts(alpha, path):
                theta=np.full(C, 0.05), nu=np.full(C, 4.0))
     got, counts = [], []
     for mfma in (False, True):
-        ns = _native(ref, C, "persistent")
+        ns = _native(ref, C)
         ns.set_debug(mfma_gram=mfma)
         ns.set_state(**st0)
         got.append(ns.eval_lnlike())
@@ -191,9 +147,8 @@ def test_low_rank_gram_alpha_gate_and_path_counts(alpha, path):
     assert counts[1] == {"low_rank": 0, "mfma": C, "large_mfma": 0}, counts[1]
     want = {"low_rank": C, "mfma": 0} if path == "low_rank" else {"low_rank": 0, "mfma": C}
     assert counts[0] == dict(want, large_mfma=0), counts[0]
-    from test_gpu_parity import _rel
     np.testing.assert_array_equal(got[0][0], got[1][0])
     if path == "mfma":
         np.testing.assert_array_equal(got[0][1], got[1][1])
     else:
-        assert np.all(_rel(got[0][1], got[1][1]) <= 1e-11), _rel(got[0][1], got[1][1]).max()
+        assert np.all(rel(got[0][1], got[1][1]) <= 1e-11), rel(got[0][1], got[1][1]).max()

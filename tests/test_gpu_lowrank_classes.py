@@ -14,17 +14,13 @@ import functools
 import numpy as np
 import pytest
 
+from gpu_support import open_sampler, single_sweep_differences
 from gibbs_student_t_amd import _abi
 from gibbs_student_t_amd.model import PTA
-from gibbs_student_t_amd.native import NativeSampler
-
-from golden_io import load_ref, sweep_state
-from test_gpu_parity import _rel
-from test_gpu_waves import KEYS
+from golden_io import sweep_state
+from support import cached_ref, prior_box, rel
 
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
 
 C = 64
 LR_MAX = 32
@@ -37,9 +33,8 @@ FLAGGED = {
 assert len(FLAGGED["lr_max"]) == LR_MAX and len(FLAGGED["lr_max_plus_1"]) == LR_MAX + 1
 
 
-@functools.lru_cache(maxsize=None)
 def _ref():
-    return load_ref("beta_fixed")
+    return cached_ref("beta_fixed")
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,17 +49,13 @@ def _pta(ncls):
 
 
 def _sampler(ncls):
-    ns = NativeSampler(_pta(ncls), _ref()["kw"], 0, path="persistent")
-    assert ns.path == "persistent"
-    ns.alloc(C)
-    return ns
+    return open_sampler(dict(pta=_pta(ncls), kw=_ref()["kw"]), C, "persistent")
 
 
 def _start(ncls, flagged, seed):
     pta = _pta(ncls)
     n = pta.n
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     z = np.zeros((C, n))
     z[:, flagged] = 1.0
     return dict(x=np.random.default_rng(seed).uniform(lo, hi, size=(C, len(lo))),
@@ -93,7 +84,7 @@ def test_low_rank_gram_classes_and_edges(ncls, flagged):
                          "large_mfma": 0}, counts[0]
     assert np.all(np.isfinite(got[1][1]))
     np.testing.assert_array_equal(got[0][0], got[1][0])
-    r = _rel(got[0][1], got[1][1])
+    r = rel(got[0][1], got[1][1])
     print(f"ncls {ncls} {flagged}: max relative difference {r.max():.3e}")
     if low:
         assert np.all(r <= 1e-11), r.max()
@@ -119,13 +110,5 @@ def test_low_rank_launch_equals_single_sweep_launches(ncls):
 
     ns = _sampler(ncls)
     ns.set_state(**st0)
-    bad = []
-    for s in range(S):
-        bad += [(s, k) for k in KEYS if not torch.equal(ns.state[k], rec[k][:, s])]
-        if bad:
-            break
-        ns.sweep(1, seed=seed, sweep0=sweep0 + s)
-    if not bad:
-        bad += [(S, k) for k in KEYS + ("status",) if not torch.equal(ns.state[k], long_state[k])]
-    ns.close()
+    bad = single_sweep_differences(ns, rec, long_state, S, seed, sweep0)
     assert not bad, f"first difference (sweep, array) {bad[:4]}"

@@ -4,30 +4,23 @@ gst_model_set_procs) on the GPU against the reference's recorded runs
 both likelihoods at every point the reference evaluated, the MH blocks and the b draw from
 every recorded start, and the 12-sweep replay against the oracle.  Tolerances are
 test_gpu_parity's: continuous outputs <= 1e-10 relative, discrete draws exact."""
-import os
-import shutil
+import ctypes as ct
+import functools
 import subprocess
 
 import numpy as np
 import pytest
 
-from golden_io import oracle_replay, sweep_state
-import mgp_io
+from gpu_support import open_sampler, replay, upload_tape
+from gibbs_student_t_amd import _abi
+from gibbs_student_t_amd.native import NativeSampler, model_desc, pack_tape
+from golden_io import MGP_DATASETS, MGP_NAMES, load_ref, oracle_replay
+from support import (RTOL, assert_b_within_reference_error, assert_lnl_within_reference_error,
+                     assert_replay_matches, cached_ref, chain_state, host_tool, rel,
+                     start_state, states_at)
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd import _abi  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler, pack_tape  # noqa: E402
-from oracle.gibbs_oracle import (ChainState, Oracle, OutlierModel,  # noqa: E402
-                                 b_mean_extended, lnlike_marginal_extended)
-from test_gpu_parity import _rel, _states, assert_replay_matches  # noqa: E402
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RTOL = 1e-10
 # the large path's hyper kernel of each dataset (tools/plan_dump.cpp names), by debug flags
 LARGE_KERNEL = {
     ("dmw", ""): "hyper_reg<16>", ("dmw", "large_hyper"): "hyper<0>",
@@ -40,38 +33,17 @@ DEBUG_BITS = {"large_hyper": _abi.DEBUG_LARGE_HYPER, "epochs_lds": _abi.DEBUG_EP
 RUNS = {"dmg": [("persistent", ""), ("large", "")], "dme": [("persistent", ""), ("large", "")],
         "dmw": [("large", ""), ("large", "large_hyper")], "dm3": [("large", "")],
         "dmx": [("large", ""), ("large", "epochs_lds"), ("large", "large_hyper")]}
-CASES = [(name, path, dbg) for name in mgp_io.NAMES for path, dbg in RUNS[name.split("_")[0]]]
+CASES = [(name, path, dbg) for name in MGP_NAMES for path, dbg in RUNS[name.split("_")[0]]]
 IDS = [f"{n}-{p}{'-' + d if d else ''}" for n, p, d in CASES]
 
 
-@pytest.fixture(scope="module")
-def refs():
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = mgp_io.load_ref(name)
-        return cache[name]
-    return get
-
-
 def _native(ref, C, path="auto", dbg=""):
-    ns = NativeSampler(ref["pta"], ref["kw"], 0, path=path)
-    assert path == "auto" or ns.path == path
-    if dbg:
-        ns.set_debug(**{dbg: True})
-    ns.alloc(C)
-    return ns
+    return open_sampler(ref, C, path, **({dbg: True} if dbg else {}))
 
 
 @pytest.fixture(scope="module")
 def plan_bin(tmp_path_factory):
-    assert shutil.which("g++"), "the kernel check needs g++ (tools/plan_dump.cpp)"
-    out = tmp_path_factory.mktemp("plan") / "plan_dump"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "gibbs_student_t_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "plan_dump.cpp"), "-o", str(out)], check=True)
-    return str(out)
+    return host_tool(tmp_path_factory, "plan_dump", required=True)
 
 
 def planned_hyper_kernel(plan_bin, pta, dbg):
@@ -90,14 +62,14 @@ def planned_hyper_kernel(plan_bin, pta, dbg):
     return " ".join(sorted(set(names), key=names.index))
 
 
-@pytest.mark.parametrize("ds", list(mgp_io.DATASETS))
-def test_path_of_each_dataset(ds, refs, plan_bin):
+@pytest.mark.parametrize("ds", list(MGP_DATASETS))
+def test_path_of_each_dataset(ds, plan_bin):
     """dmg and dme (P = 5 and 8, 24 and 44 hyper columns) run on the persistent kernel's
     general instances, the others on the large path: dmw (100 columns) on lg_hyper_reg<16>, dm3
     (130) on lg_hyper<0>, dmx (40 Fourier + 60 ECORR) epochs first on lg_hyper_ecr."""
-    ref = refs(f"{ds}_beta_fixed")
+    ref = cached_ref(f"{ds}_beta_fixed")
     pta = ref["pta"]
-    ncols, nec, path = mgp_io.DATASETS[ds]
+    ncols, nec, path = MGP_DATASETS[ds]
     assert tuple(q.ncol for q in pta.procs) == ncols and pta.n_ecorr == nec
     assert len(pta.params) <= (8 if path == "persistent" else 16)
     ns = NativeSampler(pta, ref["kw"], 0)
@@ -110,17 +82,17 @@ def test_path_of_each_dataset(ds, refs, plan_bin):
 
 
 @pytest.mark.parametrize("name,path,dbg", CASES, ids=IDS)
-def test_lnlikelihoods(name, path, dbg, refs):
+def test_lnlikelihoods(name, path, dbg):
     """get_lnlikelihood_white / get_lnlikelihood at every point the reference evaluated, on
     every kernel that takes the model.  The long-double value arbitrates where the reference's
     own fp64 value is inexact (test_gpu_parity.test_lnlikelihoods' rule), on at most a tenth of
     the points: the fixtures were chosen so (tools/mgp_conditioning.py)."""
-    ref = refs(name)
+    ref = cached_ref(name)
     tape = ref["tape"]
     S = int(ref["niter"])
     for which, K in (("white", 21), ("hyper", 11)):
         idx = np.repeat(np.arange(S), K)
-        st, ss = _states(ref, idx)
+        st, ss = states_at(ref, idx)
         xs = tape[f"{which}_lnl_x"].reshape(S * K, -1)
         want = tape[f"{which}_lnl"].reshape(-1)
         ns = _native(ref, S * K, path, dbg)
@@ -129,36 +101,31 @@ def test_lnlikelihoods(name, path, dbg, refs):
         w, h = ns.eval_lnlike()
         ns.close()
         got = w if which == "white" else h
-        r = _rel(got, want)
+        r = rel(got, want)
         print(f"{name} {path} {dbg} {which}: max rel {np.nanmax(r):.3e}")
         bad = np.flatnonzero(r > RTOL)
         assert len(bad) <= 0.1 * len(want), f"{which}: {len(bad)} of {len(want)} points arbitrated"
         for k in bad:
-            s = ss[k]
-            st_k = ChainState(b=s["b"], z=s["z"], alpha=s["alpha"], pout=s["pout"],
-                              theta=s["theta"], nu=s["nu"])
             assert which == "hyper", f"white lnL mismatch {r[k]:.3e} at {k}"
-            ext, scale = lnlike_marginal_extended(ref["pta"], st_k, xs[k], with_scale=True)
-            err = abs(got[k] - ext)
-            assert err <= max(2 * abs(want[k] - ext), RTOL * scale), \
-                f"{which}[{k}]: gpu {got[k]!r} ref {want[k]!r} extended {ext!r} scale {scale:.3e}"
+            assert_lnl_within_reference_error(ref["pta"], chain_state(ss[k]), xs[k], got[k],
+                                              want[k], f"{which}[{k}]")
 
 
 @pytest.mark.parametrize("name,path,dbg", CASES, ids=IDS)
-def test_mh_blocks_and_b_draw(name, path, dbg, refs):
+def test_mh_blocks_and_b_draw(name, path, dbg):
     """White MH + Gram + hyper MH + b draw, each sweep from the reference's recorded start: x
     bit-exact (the same MH decisions over every process's parameters), b within 1e-9 of the
     Cholesky mean plus the recorded draw term."""
-    ref = refs(name)
+    ref = cached_ref(name)
     S = int(ref["niter"])
     idx = np.arange(S)
-    st, ss = _states(ref, idx)
+    st, ss = states_at(ref, idx)
     ns = _native(ref, S, path, dbg)
     ns.set_state(x=ref["chain"][:S], theta=np.array([s["theta"] for s in ss]),
                  nu=np.array([s["nu"] for s in ss]), **st)
     rows = pack_tape(ref["tape"], idx, ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(rows[:, None, :]).to(ns.tdev).contiguous()
-    ns.sweep(1, mask=_abi.STAGE_WHITE | _abi.STAGE_HYPER | _abi.STAGE_B, tape=tape)
+    ns.sweep(1, mask=_abi.STAGE_WHITE | _abi.STAGE_HYPER | _abi.STAGE_B,
+             tape=upload_tape(ns, rows[:, None, :]))
     out = ns.get_state()
     ns.close()
     assert np.all((out["status"] & _abi.STATUS_ERRORS) == 0)
@@ -171,49 +138,28 @@ def test_mh_blocks_and_b_draw(name, path, dbg, refs):
         assert not out["status"][i] & _abi.STATUS_FLOOR
         err = np.linalg.norm(out["b"][i] - want[i]) / np.linalg.norm(want[i])
         if err > 1e-9:
-            # cond(Sigma) so large that both fp64 Cholesky means carry ~cond * eps error: the
-            # long-double mean arbitrates, allowing twice the reference's own error
-            s = ss[i]
-            st_i = ChainState(b=s["b"], z=s["z"], alpha=s["alpha"], pout=s["pout"],
-                              theta=s["theta"], nu=s["nu"])
             x_h = ref["chain"][i + 1] if i + 1 < S else out["x"][i]
-            mext = b_mean_extended(ref["pta"], st_i, x_h)
-            e_gpu = np.linalg.norm(out["b"][i] - (mext + t["b_delta"][i]))
-            e_ref = np.linalg.norm(t["b_mean_chol"][i] - mext)
-            assert e_gpu <= 2 * e_ref + 1e-12 * np.linalg.norm(mext), \
-                f"sweep {i}: b err {err:.3e} (cond {t['b_cond'][i]:.2e}), " \
-                f"vs extended {e_gpu:.3e} > 2 x ref {e_ref:.3e}"
+            assert_b_within_reference_error(
+                ref["pta"], chain_state(ss[i]), x_h, out["b"][i], t["b_mean_chol"][i],
+                t["b_delta"][i], f"sweep {i}: b err {err:.3e} (cond {t['b_cond'][i]:.2e})")
     for i in np.flatnonzero(~drew):
         np.testing.assert_array_equal(out["b"][i], ref["bchain"][i])
 
 
 @pytest.fixture(scope="module")
-def replays(refs):
-    cache = {}
-
-    def get(name):
-        if name not in cache:
-            cache[name] = oracle_replay(refs(name))
-        return cache[name]
-    return get
+def replays():
+    return functools.lru_cache(maxsize=None)(lambda name: oracle_replay(cached_ref(name)))
 
 
 @pytest.mark.parametrize("name,path,dbg", CASES, ids=IDS)
-def test_full_chain_replay_vs_oracle(name, path, dbg, refs, replays):
+def test_full_chain_replay_vs_oracle(name, path, dbg, replays):
     """The recorded sweeps on the reference's tape against the oracle replaying the same tape
     with the Cholesky-mean b draw: discrete records exact, continuous ones <= 1e-10."""
-    ref = refs(name)
+    ref = cached_ref(name)
     S = int(ref["niter"])
-    s0 = sweep_state(ref, 0)
     ns = _native(ref, 1, path, dbg)
-    ns.set_state(x=ref["xs"][None], b=s0["b"][None], z=s0["z"][None],
-                 alpha=s0["alpha"][None], pout=s0["pout"][None], theta=np.array([s0["theta"]]),
-                 nu=np.array([s0["nu"]]))
-    rows = pack_tape(ref["tape"], np.arange(S), ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(rows[None]).to(ns.tdev).contiguous()
-    rec = ns.alloc_records(S)
-    ns.sweep(S, records=rec, tape=tape)
-    got = {k: v.cpu().numpy()[0] for k, v in rec.items()}
+    ns.set_state(**start_state(ref, 1))
+    got = replay(ns, ref, S)
     ns.close()
     assert_replay_matches(got, replays(name), ref, name)
 
@@ -222,26 +168,18 @@ def test_full_chain_replay_vs_oracle(name, path, dbg, refs, replays):
 def test_one_process_is_the_legacy_entry(name):
     """gst_model_set_procs with nproc = 1 gives bitwise the chains of gst_model_set_batch on a
     classic, a GEN and a large-path model: 20 Philox sweeps of 8 chains."""
-    import ctypes as ct
-
-    from golden_io import load_ref
     ref = load_ref(name)
-    s0 = sweep_state(ref, 0)
     outs = []
     for procs in (False, True):
         ns = NativeSampler(ref["pta"], ref["kw"], 0)
         assert ns.procs.nproc == 1
         if procs:
-            from gibbs_student_t_amd.native import model_desc
             desc, keep = model_desc(ref["pta"], ref["kw"])
             arr = (_abi.ModelDesc * 1)(desc)
             _abi.check(ns.lib, ns.lib.gst_model_set_procs(ns.ctx, arr, ct.byref(keep["procs"]), 1),
                        "gst_model_set_procs")
         ns.alloc(8)
-        ns.set_state(x=np.tile(ref["xs"], (8, 1)), b=np.tile(s0["b"], (8, 1)),
-                     z=np.tile(s0["z"], (8, 1)), alpha=np.tile(s0["alpha"], (8, 1)),
-                     pout=np.tile(s0["pout"], (8, 1)), theta=np.full(8, s0["theta"]),
-                     nu=np.full(8, s0["nu"]))
+        ns.set_state(**start_state(ref, 8))
         rec = ns.alloc_records(20)
         ns.sweep(20, records=rec, seed=77)
         outs.append(({k: v.cpu().numpy() for k, v in rec.items()}, ns.get_state(), ns.path))

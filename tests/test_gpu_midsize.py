@@ -1,6 +1,6 @@
 """Mid-size pulsars on the large path: the one-wave-per-chain kernels against the
-generic ones they replace, at n = 1000 (the large path forced: since round 3 the persistent
-kernel's 16-slot instance takes pulsars of up to 1024 TOAs).
+generic ones they replace, at n = 1000 (the large path forced: the persistent kernel's 16-slot
+instance takes pulsars of up to 1024 TOAs).
 
 * lg_gram_small must give bitwise lg_gram's Gram: whole chains are compared bitwise with the
   generic Gram forced (GST_DEBUG_LARGE_GRAM).
@@ -10,15 +10,23 @@ kernel's 16-slot instance takes pulsars of up to 1024 TOAs).
 The kernels' parity with the reference itself is covered by the large-path replays of
 test_gpu_parity.py, whose fixtures (m = 74) run on these same kernels.
 """
+import os
+import warnings
+
 import numpy as np
 import pytest
+import scipy.stats
 
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
+from gpu_support import open_sampler
 from gibbs_student_t_amd import data
+from gibbs_student_t_amd._abi import STATUS_ERRORS
 from gibbs_student_t_amd.model import PTA
 from gibbs_student_t_amd.native import NativeSampler
+from gibbs_student_t_amd.run_sims import MODELS
+from golden_io import GOLDEN, load_dataset, load_ref
+from oracle.gibbs_oracle import ChainState, Oracle, OutlierModel, lnlike_marginal_extended
+from support import prior_box, start_state
 
-torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 CFG = dict(model="mixture", vary_df=True, theta_prior="beta")
@@ -27,8 +35,6 @@ C, S = 16, 6
 
 @pytest.fixture(scope="module")
 def pta():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
     return PTA(data.scaled_synthetic(n=1000, components=30, ntm=14, seed=11), components=30)
 
 
@@ -37,8 +43,7 @@ def _run(pta, **debug):
     ns.set_debug(**debug)
     ns.alloc(C)
     rng = np.random.default_rng(5)
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     x0 = rng.uniform(lo, hi, size=(C, len(lo)))
     ns.set_state(x=x0, z=np.zeros((C, ns.n)), alpha=np.ones((C, ns.n)),
                  theta=np.full(C, 0.05), nu=np.full(C, 4.0))
@@ -90,20 +95,11 @@ def test_register_hyper_matches_lds_hyper_ecorr(name):
     lg_hyper_reg<8>) and 120 (scaled: 60 components: lg_hyper_reg<16>, two columns per lane;
     mb's 20 + 60 ECORR columns take lg_hyper<2>, the tests below); their parity with the
     reference itself is test_gpu_parity.py's large-path replays."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    from golden_io import load_ref, sweep_state
     ref = load_ref(name)
-    s0 = sweep_state(ref, 0)
     outs = []
     for large_hyper in (False, True):
-        ns = NativeSampler(ref["pta"], ref["kw"], 0, path="large")
-        ns.set_debug(large_hyper=large_hyper)
-        ns.alloc(C)
-        ns.set_state(x=np.tile(ref["xs"], (C, 1)), b=np.tile(s0["b"], (C, 1)),
-                     z=np.tile(s0["z"], (C, 1)), alpha=np.tile(s0["alpha"], (C, 1)),
-                     pout=np.tile(s0["pout"], (C, 1)), theta=np.full(C, s0["theta"]),
-                     nu=np.full(C, s0["nu"]))
+        ns = open_sampler(ref, C, "large", large_hyper=large_hyper)
+        ns.set_state(**start_state(ref, C))
         rec = ns.alloc_records(S)
         ns.sweep(S, records=rec, seed=33)
         out = {k: v.cpu().numpy() for k, v in rec.items()}
@@ -136,24 +132,12 @@ def test_epochs_first_hyper_matches_blocked_hyper(name):
     different orders, so their Philox b draws are different (equally distributed) draws and
     the chains are compared with the reference instead: test_gpu_parity.py's large-path
     likelihood, MH / b-draw (recorded draw term) and replay tests run on lg_hyper<2>."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    from golden_io import load_ref, sweep_state
     ref = load_ref(name)
-    pta = ref["pta"]
-    s0 = sweep_state(ref, 0)
     C2 = 256
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
-    x = np.random.default_rng(5).uniform(lo, hi, size=(C2, len(lo)))
     got = []
     for large_hyper in (False, True):
-        ns = NativeSampler(pta, ref["kw"], 0, path="large")
-        ns.set_debug(large_hyper=large_hyper)
-        ns.alloc(C2)
-        ns.set_state(x=x, b=np.tile(s0["b"], (C2, 1)), z=np.tile(s0["z"], (C2, 1)),
-                     alpha=np.tile(s0["alpha"], (C2, 1)), pout=np.tile(s0["pout"], (C2, 1)),
-                     theta=np.full(C2, s0["theta"]), nu=np.full(C2, s0["nu"]))
+        ns = open_sampler(ref, C2, "large", large_hyper=large_hyper)
+        ns.set_state(**start_state(ref, C2, 5))
         w, h = ns.eval_lnlike()
         got.append((np.asarray(w), np.asarray(h)))
         ns.close()
@@ -172,15 +156,9 @@ def test_epochs_first_hyper_draws_match_blocked_hyper(dataset):
     same start through lg_hyper<2> and the generic kernel must have the same marginal law at
     every sweep (converged or not): 1024 chains from prior draws, after 150 sweeps, every
     sampled parameter plus theta, nu and two b components, two-sample KS p > 1e-3."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import scipy.stats
-    from golden_io import load_dataset
-    from gibbs_student_t_amd.run_sims import MODELS
     pta = load_dataset(dataset=dataset)
     C2, S2 = 1024, 150
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
+    lo, hi = prior_box(pta)
     x0 = np.random.default_rng(9).uniform(lo, hi, size=(C2, len(lo)))
     fin = []
     for large_hyper in (False, True):
@@ -206,19 +184,11 @@ def test_epochs_first_hyper_draws_match_blocked_hyper(dataset):
 def test_overlapping_ecorr_epochs_take_the_general_elimination():
     """lg_hyper<2> eliminates ECORR epochs first because disjoint epochs make the ECORR block
     of T^T N^-1 T diagonal.  A basis where TOAs sit in two ECORR columns
-    (nothing enforced it) must run the general elimination instead: the ebig
+    (nothing else enforces it) must run the general elimination instead: the ebig
     dataset with every 5th TOA also in the next epoch's column, on the large path, gives the
     b-marginalised likelihood of the oracle (gibbs.py:288-329) at 64 prior draws, within
     1e-9 relative or the fp64 oracle's own error against the long-double evaluation; the
     disjoint original keeps the epochs-first kernel, same check."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    import os
-    import warnings
-    from golden_io import GOLDEN
-    from oracle.gibbs_oracle import (ChainState, Oracle, OutlierModel,
-                                     lnlike_marginal_extended)
-    from gibbs_student_t_amd.run_sims import MODELS
     d = dict(np.load(os.path.join(GOLDEN, "ebig_dataset.npz"), allow_pickle=False))
     nec = int(d["n_ecorr"])
     for overlap in (False, True):
@@ -240,8 +210,7 @@ def test_overlapping_ecorr_epochs_take_the_general_elimination():
                               n_ecorr=nec, ecorr_backend=d["ecorr_backend"],
                               log10_ecorr=tuple(d["log10_ecorr"]) or None)
         C2 = 64
-        lo = np.array([p.pmin for p in pta.params])
-        hi = np.array([p.pmax for p in pta.params])
+        lo, hi = prior_box(pta)
         x = np.random.default_rng(8).uniform(lo, hi, size=(C2, len(lo)))
         ns = NativeSampler(pta, MODELS["beta"], 0, path="large")
         ns.alloc(C2)
@@ -268,7 +237,7 @@ def test_overlapping_ecorr_epochs_take_the_general_elimination():
 @pytest.mark.parametrize("name", ["ebig_beta_fixed", "ebig_t_fixed", "mb_beta_fixed",
                                   "mb_t_fixed", "mbn_vvh17_fixed"])
 def test_register_epochs_first_matches_lds_epochs_first(name):
-    """lg_hyper_ecr (round 6: the epochs-first elimination on one wave per chain, register-
+    """lg_hyper_ecr (the epochs-first elimination on one wave per chain, register-
     resident 8x8-cyclic factor, the epochs' rank-1 downdates on the VALU) against lg_hyper<2>
     (256 threads, LDS, MFMA rank update; GST_DEBUG_EPOCHS_LDS): the same elimination order
     [ECORR | TM | Fourier] and Philox normals, so the b-marginalised likelihood agrees to
@@ -285,8 +254,6 @@ def test_wide_register_epochs_first_matches_lds_epochs_first():
     (<= 76), 80 epochs (>= 55) and 120 hyper columns (> 62): hyper class 2, and 16 + 40 = 56
     X rows past lg_hyper_ecr<6,46>'s 46.  16 chains x 6 sweeps from prior draws, held to
     _compare_large_variants' tolerances."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
     psr = data.multiband(nepochs=80, nsub=4, seed=7, components=20)
     wide = PTA(psr, components=20, efac=(0.2, 10.0), log10_equad=(-10.0, -5.0),
                log10_A=(-18.0, -12.0), gamma=(0.0, 7.0), log10_ecorr=(-8.0, -5.0), ecorr_dt=30.0)
@@ -300,7 +267,7 @@ def test_wide_register_epochs_first_matches_lds_epochs_first():
 @pytest.mark.parametrize("name", ["ebig_beta_fixed", "ebig_t_fixed", "mb_beta_fixed",
                                   "mb_t_fixed", "mbn_vvh17_fixed"])
 def test_structured_ecorr_gram_matches_dense_gram(name):
-    """lg_gram_ec (round 6: for disjoint ECORR epochs run epochs first, only G_xx, the epochs'
+    """lg_gram_ec (for disjoint ECORR epochs run epochs first, only G_xx, the epochs'
     diagonal and their couplings to [timing model | Fourier | r], by MFMA over the compact
     columns and over the epoch-ordered TOAs) against the dense Gram (GST_DEBUG_LARGE_GRAM:
     lg_gram / lg_gram_small over all mp columns): the same hyper kernel on Grams that differ
@@ -311,33 +278,16 @@ def test_structured_ecorr_gram_matches_dense_gram(name):
 def _compare_large_variants(name, dbg_a, dbg_b):
     """Likelihoods at 256 states and 16 chains x 6 sweeps of two large-path builds of the same
     chain (debug flags dbg_a, dbg_b) from the fixture's start."""
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-    from golden_io import load_ref, sweep_state
     ref = load_ref(name)
-    pta = ref["pta"]
-    s0 = sweep_state(ref, 0)
     C2 = 256
-    lo = np.array([p.pmin for p in pta.params])
-    hi = np.array([p.pmax for p in pta.params])
-    x = np.random.default_rng(12).uniform(lo, hi, size=(C2, len(lo)))
     got, outs = [], []
     for dbg in (dbg_a, dbg_b):
-        ns = NativeSampler(pta, ref["kw"], 0, path="large")
-        ns.set_debug(**dbg)
-        ns.alloc(C2)
-        ns.set_state(x=x, b=np.tile(s0["b"], (C2, 1)), z=np.tile(s0["z"], (C2, 1)),
-                     alpha=np.tile(s0["alpha"], (C2, 1)), pout=np.tile(s0["pout"], (C2, 1)),
-                     theta=np.full(C2, s0["theta"]), nu=np.full(C2, s0["nu"]))
+        ns = open_sampler(ref, C2, "large", **dbg)
+        ns.set_state(**start_state(ref, C2, 12))
         got.append(ns.eval_lnlike())
         ns.close()
-        ns = NativeSampler(pta, ref["kw"], 0, path="large")
-        ns.set_debug(**dbg)
-        ns.alloc(C)
-        ns.set_state(x=np.tile(ref["xs"], (C, 1)), b=np.tile(s0["b"], (C, 1)),
-                     z=np.tile(s0["z"], (C, 1)), alpha=np.tile(s0["alpha"], (C, 1)),
-                     pout=np.tile(s0["pout"], (C, 1)), theta=np.full(C, s0["theta"]),
-                     nu=np.full(C, s0["nu"]))
+        ns = open_sampler(ref, C, "large", **dbg)
+        ns.set_state(**start_state(ref, C))
         rec = ns.alloc_records(S)
         ns.sweep(S, records=rec, seed=35)
         out = {k: v.cpu().numpy() for k, v in rec.items()}

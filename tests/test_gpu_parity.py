@@ -8,42 +8,26 @@ large (SURVEY.md 8a R6 parity note), so it is used only for well-conditioned swe
 """
 import numpy as np
 import pytest
+import scipy.linalg as sl
 
+from gpu_support import open_sampler, replay, upload_tape
+from gibbs_student_t_amd import _abi
+from gibbs_student_t_amd._abi import STATUS_ERRORS
+from gibbs_student_t_amd.native import STATE_KEYS, NativeSampler, pack_tape
 from golden_io import fixture_names, load_ref, oracle_replay, sweep_state
+from oracle.gibbs_oracle import Oracle, OutlierModel
+from support import (PATHS, RTOL, assert_b_within_reference_error,
+                     assert_floor_draw_within_reference_error,
+                     assert_lnl_within_reference_error, assert_replay_matches, chain_state,
+                     prior_box, rel, start_state, states_at)
 
 pytestmark = pytest.mark.gpu
 
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
-from gibbs_student_t_amd import _abi  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler, pack_tape  # noqa: E402
-import scipy.linalg as sl  # noqa: E402
-
-from oracle.gibbs_oracle import (ChainState, Oracle, OutlierModel,  # noqa: E402
-                                 b_mean_extended, lnlike_marginal_extended)
-
 NAMES = fixture_names()
-RTOL = 1e-10
-
-
-PATHS = ("persistent", "large")
 
 
 def _native(ref, C, path="auto"):
-    try:
-        ns = NativeSampler(ref["pta"], ref["kw"], 0, path=path)
-    except _abi.GstNativeError as e:
-        # the persistent kernel's instances (gst_shapes.h) do not cover this model: its
-        # parity runs on the large path only (test_general_white_noise_path_choice pins which)
-        if path == "persistent" and "no persistent-kernel instance" in str(e):
-            pytest.skip("beyond the persistent kernel's shapes (large path only)")
-        raise
-    assert path == "auto" or ns.path == path
-    ns.alloc(C)
-    return ns
+    return open_sampler(ref, C, path, skip_if_no_instance=True)
 
 
 @pytest.mark.parametrize("name", [n for n in NAMES
@@ -58,32 +42,16 @@ def test_general_white_noise_path_choice(name):
     ns = NativeSampler(ref["pta"], ref["kw"], 0)
     assert ns.path == ("persistent" if name.startswith(("ecb", "ecn", "ecq", "jb")) else "large")
     if ns.path == "persistent":
-        # two waves per chain (round 6: the general white-noise instances have the pair build;
-        # bitwise equality with one wave is test_gpu_waves.py's): forced and automatic both run
+        # two waves per chain (the general white-noise instances have the pair build; bitwise
+        # equality with one wave is test_gpu_waves.py's): forced and automatic both run
         ns.alloc(8)
-        s0 = sweep_state(ref, 0)
-        ns.set_state(x=np.tile(ref["chain"][0], (8, 1)), b=np.tile(s0["b"], (8, 1)),
-                     z=np.tile(s0["z"], (8, 1)), alpha=np.tile(s0["alpha"], (8, 1)),
-                     pout=np.tile(s0["pout"], (8, 1)), theta=np.full(8, s0["theta"]),
-                     nu=np.full(8, s0["nu"]))
+        ns.set_state(**start_state(ref, 8, "chain0"))
         ns.set_waves(2)
         ns.sweep(1, seed=1)
         ns.set_waves("auto")
         ns.sweep(1, seed=1, sweep0=1)
         assert np.all((ns.get_state()["status"] & _abi.STATUS_ERRORS) == 0)
     ns.close()
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, float), np.asarray(b, float)
-    both_inf = np.isinf(a) & np.isinf(b) & (np.sign(a) == np.sign(b))
-    d = np.where(both_inf, 0.0, np.abs(a - b) / np.maximum(np.abs(b), 1e-300))
-    return d
-
-
-def _states(ref, idx):
-    ss = [sweep_state(ref, i) for i in idx]
-    return {k: np.stack([s[k] for s in ss]) for k in ("b", "z", "alpha", "pout")}, ss
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -95,7 +63,7 @@ def test_lnlikelihoods(name, path):
     S = int(ref["niter"])
     for which, K in (("white", 21), ("hyper", 11)):
         idx = np.repeat(np.arange(S), K)
-        st, ss = _states(ref, idx)
+        st, ss = states_at(ref, idx)
         xs = tape[f"{which}_lnl_x"].reshape(S * K, -1)
         want = tape[f"{which}_lnl"].reshape(-1)
         ns = _native(ref, S * K, path)
@@ -103,21 +71,13 @@ def test_lnlikelihoods(name, path):
                      nu=np.array([s["nu"] for s in ss]), **st)
         w, h = ns.eval_lnlike()
         got = w if which == "white" else h
-        r = _rel(got, want)
+        r = rel(got, want)
         bad = np.flatnonzero(r > RTOL)
         for k in bad:
-            # ill-conditioned Sigma: the reference's own fp64 value is inexact.  Arbitrate
-            # with the long-double value: the GPU error must be within twice the
-            # reference's own error, or within 1e-10 of the magnitude of the cancelling
-            # terms (log|N|, r^T N^-1 r, d^T Sigma^-1 d, log|Sigma|, log|phi|)
-            s = ss[k]
-            st_k = ChainState(b=s["b"], z=s["z"], alpha=s["alpha"], pout=s["pout"],
-                              theta=s["theta"], nu=s["nu"])
+            # ill-conditioned Sigma: the reference's own fp64 value is inexact
             assert which == "hyper", f"white lnL mismatch {r[k]:.3e} at {k}"
-            ext, scale = lnlike_marginal_extended(ref["pta"], st_k, xs[k], with_scale=True)
-            err = abs(got[k] - ext)
-            assert err <= max(2 * abs(want[k] - ext), RTOL * scale), \
-                f"{which}[{k}]: gpu {got[k]!r} ref {want[k]!r} extended {ext!r} scale {scale:.3e}"
+            assert_lnl_within_reference_error(ref["pta"], chain_state(ss[k]), xs[k], got[k],
+                                              want[k], f"{which}[{k}]")
         ns.close()
 
 
@@ -128,13 +88,13 @@ def test_mh_blocks_and_b_draw(name, path):
     ref = load_ref(name)
     S = int(ref["niter"])
     idx = np.arange(S)
-    st, ss = _states(ref, idx)
+    st, ss = states_at(ref, idx)
     ns = _native(ref, S, path)
     ns.set_state(x=ref["chain"][:S], theta=np.array([s["theta"] for s in ss]),
                  nu=np.array([s["nu"] for s in ss]), **st)
     rows = pack_tape(ref["tape"], idx, ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(rows[:, None, :]).to(ns.tdev).contiguous()
-    ns.sweep(1, mask=_abi.STAGE_WHITE | _abi.STAGE_HYPER | _abi.STAGE_B, tape=tape)
+    ns.sweep(1, mask=_abi.STAGE_WHITE | _abi.STAGE_HYPER | _abi.STAGE_B,
+             tape=upload_tape(ns, rows[:, None, :]))
     out = ns.get_state()
     assert np.all((out["status"] & _abi.STATUS_ERRORS) == 0)
     # x after the hyper block == the next sweep's recorded x: exact (same MH decisions)
@@ -144,9 +104,7 @@ def test_mh_blocks_and_b_draw(name, path):
     want = t["b_mean_chol"] + t["b_delta"]
     orc = Oracle(ref["pta"], OutlierModel(**ref["kw"]))
     for i in np.flatnonzero(drew):
-        s = ss[i]
-        st_i = ChainState(b=s["b"], z=s["z"], alpha=s["alpha"], pout=s["pout"],
-                          theta=s["theta"], nu=s["nu"])
+        st_i = chain_state(ss[i])
         x_h = ref["chain"][i + 1] if i + 1 < S else out["x"][i]
         orc.cache = None
         Sigma, d = orc.sigma_matrix(st_i, x_h)
@@ -165,41 +123,14 @@ def test_mh_blocks_and_b_draw(name, path):
             continue
         err = np.linalg.norm(out["b"][i] - want[i]) / np.linalg.norm(want[i])
         if err > 1e-9:
-            # cond(Sigma) so large that fp64 Cholesky means (LAPACK's and ours) both carry
-            # ~cond*eps error: arbitrate with the long-double mean, allowing twice the
-            # reference's own error
-            mext = b_mean_extended(ref["pta"], st_i, x_h)
-            e_gpu = np.linalg.norm(out["b"][i] - (mext + t["b_delta"][i]))
-            e_ref = np.linalg.norm(t["b_mean_chol"][i] - mext)
-            assert e_gpu <= 2 * e_ref + 1e-12 * np.linalg.norm(mext), \
-                f"sweep {i}: b err {err:.3e} (cond {t['b_cond'][i]:.2e}), " \
-                f"vs extended {e_gpu:.3e} > 2 x ref {e_ref:.3e}"
+            assert_b_within_reference_error(
+                ref["pta"], st_i, x_h, out["b"][i], t["b_mean_chol"][i], t["b_delta"][i],
+                f"sweep {i}: b err {err:.3e} (cond {t['b_cond'][i]:.2e})")
         if t["b_cond"][i] < 1e7:
             err_svd = np.linalg.norm(out["b"][i] - t["b_ref"][i]) / np.linalg.norm(t["b_ref"][i])
             assert err_svd <= 1e-9
     for i in np.flatnonzero(~drew):
         np.testing.assert_array_equal(out["b"][i], ref["bchain"][i])
-
-
-def assert_floor_draw_within_reference_error(b_gpu, t, i, Sigma, d, f):
-    """A b draw at the SVD noise floor against the reference's OWN b (``b_ref``, its SVD draw
-    u (u^T d / s) + U S^-1/2 xi, gibbs.py:166-180) on the same sweep: the GPU b must be no
-    further from it than the exact draw (cho_solve(Sigma, d) + the same draw term) is, or the
-    shift f I must lie within the reference's own SVD error -- the perturbation
-    ||U S U^T - Sigma||_2 that LAPACK's SVD itself makes of Sigma on this sweep (long-double
-    reconstruction of the recomputed SVD, which must be bitwise the fixture's)."""
-    b_ref = t["b_ref"][i]
-    e_gpu = np.linalg.norm(b_gpu - b_ref)
-    e_exact = np.linalg.norm(t["b_mean_chol"][i] + t["b_delta"][i] - b_ref)
-    if e_gpu <= e_exact:
-        return
-    u, sv, _ = sl.svd(Sigma)
-    np.testing.assert_array_equal(u @ ((u.T @ d) / sv), t["b_mean_svd"][i])
-    ld = np.longdouble
-    E = (u.astype(ld) * sv.astype(ld)) @ u.T.astype(ld) - Sigma.astype(ld)
-    e_svd = np.linalg.norm(E.astype(np.float64), 2)
-    assert f <= e_svd, (f"sweep {i}: floor b {e_gpu:.3e} from the reference's b (exact draw "
-                        f"{e_exact:.3e}) and f {f:.3e} > the SVD's own error {e_svd:.3e}")
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -217,9 +148,8 @@ def test_outlier_stages(name, path):
                  pout=np.stack([s["pout"] for s in pre]),
                  theta=np.array([s["theta"] for s in pre]), nu=np.array([s["nu"] for s in pre]))
     rows = pack_tape(ref["tape"], idx, ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(rows[:, None, :]).to(ns.tdev).contiguous()
     ns.sweep(1, mask=_abi.STAGE_THETA | _abi.STAGE_Z | _abi.STAGE_ALPHA | _abi.STAGE_DF,
-             tape=tape)
+             tape=upload_tape(ns, rows[:, None, :]))
     out = ns.get_state()
     want = {k: np.stack([np.asarray(s[k], float) for s in post]) for k in
             ("z", "alpha", "pout", "theta", "nu")}
@@ -227,7 +157,7 @@ def test_outlier_stages(name, path):
     np.testing.assert_array_equal(out["nu"], want["nu"])
     np.testing.assert_array_equal(out["theta"], want["theta"])
     for k in ("alpha", "pout"):
-        r = _rel(out[k], want[k])
+        r = rel(out[k], want[k])
         assert np.all(r <= RTOL), f"{k}: max rel {r.max():.3e}"
 
 
@@ -244,16 +174,9 @@ def test_full_chain_replay(name, path):
     test_full_chain_replay_vs_oracle."""
     ref = load_ref(name)
     S = int(ref["niter"])
-    s0 = sweep_state(ref, 0)
     ns = _native(ref, 1, path)
-    ns.set_state(x=ref["xs"][None], b=s0["b"][None], z=s0["z"][None],
-                 alpha=s0["alpha"][None], pout=s0["pout"][None], theta=np.array([s0["theta"]]),
-                 nu=np.array([s0["nu"]]))
-    rows = pack_tape(ref["tape"], np.arange(S), ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(rows[None]).to(ns.tdev).contiguous()
-    rec = ns.alloc_records(S)
-    ns.sweep(S, records=rec, tape=tape)
-    got = {k: v.cpu().numpy()[0] for k, v in rec.items()}
+    ns.set_state(**start_state(ref, 1))
+    got = replay(ns, ref, S)
     np.testing.assert_array_equal(got["x"], ref["chain"])
     np.testing.assert_array_equal(got["z"], ref["zchain"])
     np.testing.assert_array_equal(got["nu"], ref["dfchain"])
@@ -262,42 +185,8 @@ def test_full_chain_replay(name, path):
     eb = np.linalg.norm(got["b"] - ref["bchain"], axis=1) / np.where(nb > 0, nb, 1.0)
     assert np.all(eb <= tol), f"b: max normwise rel {eb.max():.3e} > {tol:.1e}"
     for k, rk in (("alpha", "alphachain"), ("pout", "poutchain"), ("theta", "thetachain")):
-        r = _rel(got[k], ref[rk])
+        r = rel(got[k], ref[rk])
         assert np.all(r <= tol), f"{k}: max rel {r.max():.3e} > {tol:.1e}"
-
-
-def assert_replay_matches(got, want, ref, label=""):
-    """Discrete records exact; b normwise per sweep, alpha / pout elementwise <= RTOL.
-
-    Where the two fp64 Cholesky means (LAPACK's in the oracle, the kernel's) differ by more
-    than RTOL -- cond(Sigma) ~ 1e8 leaves both ~1e-10 from the exact mean -- the long-double
-    mean arbitrates, as in test_mh_blocks_and_b_draw: the GPU b must then be at least as
-    close to it as the oracle's (within twice its error)."""
-    n = want["z"].shape[-1]
-    for k in ("x", "z", "nu", "theta"):
-        g = got[k][..., :n] if k == "z" else got[k]
-        np.testing.assert_array_equal(g, want[k], err_msg=f"{label} {k}")
-    eb = np.linalg.norm(got["b"] - want["b"], axis=1) / np.maximum(
-        np.linalg.norm(want["b"], axis=1), 1e-300)
-    delta = ref["tape"]["b_delta"]
-    orc = Oracle(ref["pta"], OutlierModel(**ref["kw"]))
-    for k in np.flatnonzero(eb > RTOL):
-        assert k >= 1, f"{label} b differs at the start state"
-        # b recorded at sweep k was drawn in sweep k-1 at that sweep's (z, alpha) and x_k
-        st = ChainState(b=want["b"][k - 1], z=want["z"][k - 1], alpha=want["alpha"][k - 1],
-                        pout=want["pout"][k - 1], theta=float(want["theta"][k - 1]),
-                        nu=float(want["nu"][k - 1]))
-        orc.cache = None
-        f = orc.floor_shift(orc.sigma_matrix(st, want["x"][k])[0])   # the draw's floor shift
-        exact = b_mean_extended(ref["pta"], st, want["x"][k], shift=f) + delta[k - 1]
-        e_gpu = np.linalg.norm(got["b"][k] - exact)
-        e_orc = np.linalg.norm(want["b"][k] - exact)
-        assert e_gpu <= 2 * e_orc + 1e-13 * np.linalg.norm(exact), \
-            f"{label} b sweep {k}: rel {eb[k]:.3e}, |gpu - exact| {e_gpu:.3e} > " \
-            f"2 |oracle - exact| {e_orc:.3e}"
-    for k in ("alpha", "pout"):
-        r = _rel(got[k][..., :n], want[k])
-        assert np.all(r <= RTOL), f"{label} {k}: max rel {r.max():.3e}"
 
 
 @pytest.mark.parametrize("name", [n for n in NAMES if "fixed" in n])
@@ -309,28 +198,19 @@ def test_full_chain_replay_vs_oracle(name, path):
     <= 1e-10 relative (b normwise per sweep, alpha / pout / theta elementwise)."""
     ref = load_ref(name)
     S = int(ref["niter"])
-    s0 = sweep_state(ref, 0)
     ns = _native(ref, 1, path)
-    ns.set_state(x=ref["xs"][None], b=s0["b"][None], z=s0["z"][None],
-                 alpha=s0["alpha"][None], pout=s0["pout"][None], theta=np.array([s0["theta"]]),
-                 nu=np.array([s0["nu"]]))
-    rows = pack_tape(ref["tape"], np.arange(S), ns.n, ns.m, ns.stride)
-    tape = torch.as_tensor(rows[None]).to(ns.tdev).contiguous()
-    rec = ns.alloc_records(S)
-    ns.sweep(S, records=rec, tape=tape)
-    got = {k: v.cpu().numpy()[0] for k, v in rec.items()}
+    ns.set_state(**start_state(ref, 1))
+    got = replay(ns, ref, S)
     ns.close()
     assert_replay_matches(got, oracle_replay(ref, S), ref, name)
 
 
-@pytest.mark.parametrize("path", PATHS)
-def test_failed_factor_never_draws_b(path):
-    """Sigma not positive definite at the hyper block's start (negative noise weights) and
-    every proposal out of the prior: no factor exists to draw b from, so the chain keeps
-    its b and flags status 2 (gibbs.py:320-324 gives -inf; it never reaches a b draw)."""
-    ref = load_ref("beta_fixed")
+def _failed_factor_keeps_b(name, path, debug=None):
+    ref = load_ref(name)
     s0 = sweep_state(ref, 0)
     ns = _native(ref, 1, path)
+    if debug is not None:
+        ns.set_debug(**debug)
     alpha = np.full_like(s0["alpha"], -1.0)            # N = alpha^z N0 < 0 where z = 1
     b0 = np.linspace(-1e-7, 1e-7, ns.m)[None]
     ns.set_state(x=ref["xs"][None], b=b0, z=np.ones_like(s0["z"])[None], alpha=alpha[None],
@@ -339,13 +219,21 @@ def test_failed_factor_never_draws_b(path):
     rows = pack_tape(ref["tape"], [0], ns.n, ns.m, ns.stride)
     for step in range(10):
         rows[0, _abi.TAPE_HYPER + 4 * step + 2] = 1e6     # jump far outside the prior box
-    tape = torch.as_tensor(rows[:, None, :]).to(ns.tdev).contiguous()
-    ns.sweep(1, mask=_abi.STAGE_HYPER | _abi.STAGE_B | _abi.STAGE_B_FORCE, tape=tape)
+    ns.sweep(1, mask=_abi.STAGE_HYPER | _abi.STAGE_B | _abi.STAGE_B_FORCE,
+             tape=upload_tape(ns, rows[:, None, :]))
     out = ns.get_state()
     assert out["status"][0] & 2 and out["status"][0] & 1
     np.testing.assert_array_equal(out["b"], b0)
     np.testing.assert_array_equal(out["x"][0], ref["xs"])
     ns.close()
+
+
+@pytest.mark.parametrize("path", PATHS)
+def test_failed_factor_never_draws_b(path):
+    """Sigma not positive definite at the hyper block's start (negative noise weights) and
+    every proposal out of the prior: no factor exists to draw b from, so the chain keeps
+    its b and flags status 2 (gibbs.py:320-324 gives -inf; it never reaches a b draw)."""
+    _failed_factor_keeps_b("beta_fixed", path)
 
 
 @pytest.mark.parametrize("name,debug", [("scaled_beta_fixed", {}),
@@ -359,25 +247,7 @@ def test_failed_factor_never_draws_b_large_variants(name, debug):
     lg_hyper<0> (its own copy of the MH loop), the blocked lg_hyper<1> (ebig), the epochs-first
     lg_hyper<2> and lg_hyper_ecr<6,46> (mb).  Every loop on their failed-pivot paths has a fixed
     trip count (pivots only enter as data), so NaN / negative pivots end in the flags."""
-    ref = load_ref(name)
-    s0 = sweep_state(ref, 0)
-    ns = _native(ref, 1, "large")
-    ns.set_debug(**debug)
-    alpha = np.full_like(s0["alpha"], -1.0)            # N = alpha^z N0 < 0 where z = 1
-    b0 = np.linspace(-1e-7, 1e-7, ns.m)[None]
-    ns.set_state(x=ref["xs"][None], b=b0, z=np.ones_like(s0["z"])[None], alpha=alpha[None],
-                 pout=s0["pout"][None], theta=np.array([s0["theta"]]),
-                 nu=np.array([s0["nu"]]))
-    rows = pack_tape(ref["tape"], [0], ns.n, ns.m, ns.stride)
-    for step in range(10):
-        rows[0, _abi.TAPE_HYPER + 4 * step + 2] = 1e6     # jump far outside the prior box
-    tape = torch.as_tensor(rows[:, None, :]).to(ns.tdev).contiguous()
-    ns.sweep(1, mask=_abi.STAGE_HYPER | _abi.STAGE_B | _abi.STAGE_B_FORCE, tape=tape)
-    out = ns.get_state()
-    assert out["status"][0] & 2 and out["status"][0] & 1
-    np.testing.assert_array_equal(out["b"], b0)
-    np.testing.assert_array_equal(out["x"][0], ref["xs"])
-    ns.close()
+    _failed_factor_keeps_b(name, "large", debug)
 
 
 @pytest.mark.parametrize("path", PATHS)
@@ -385,11 +255,7 @@ def test_philox_mode_runs_and_moves(path):
     ref = load_ref("beta_fixed")
     C, S = 256, 50
     ns = _native(ref, C, path)
-    s0 = sweep_state(ref, 0)
-    ns.set_state(x=np.tile(ref["xs"], (C, 1)), b=np.tile(s0["b"], (C, 1)),
-                 z=np.tile(s0["z"], (C, 1)), alpha=np.tile(s0["alpha"], (C, 1)),
-                 pout=np.tile(s0["pout"], (C, 1)), theta=np.full(C, s0["theta"]),
-                 nu=np.full(C, s0["nu"]))
+    ns.set_state(**start_state(ref, C))
     rec = ns.alloc_records(S)
     ns.sweep(S, records=rec, seed=1234)
     x = rec["x"].cpu().numpy()
@@ -399,8 +265,7 @@ def test_philox_mode_runs_and_moves(path):
     # chains decorrelate from the common start
     assert np.std(x[:, -1, :], axis=0).min() > 0
     names = ref["pta"].param_names
-    lo = np.array([p.pmin for p in ref["pta"].params])
-    hi = np.array([p.pmax for p in ref["pta"].params])
+    lo, hi = prior_box(ref["pta"])
     assert np.all((x >= lo) & (x <= hi)), names
 
 
@@ -409,11 +274,7 @@ def test_sharding_invariance(path):
     """Chains keyed by global id: one launch of C == two launches of C/2 (bitwise)."""
     ref = load_ref("uniform_prior")
     C, S = 16, 5
-    s0 = sweep_state(ref, 0)
-    init = dict(x=np.tile(ref["xs"], (C, 1)), b=np.tile(s0["b"], (C, 1)),
-                z=np.tile(s0["z"], (C, 1)), alpha=np.tile(s0["alpha"], (C, 1)),
-                pout=np.tile(s0["pout"], (C, 1)), theta=np.full(C, s0["theta"]),
-                nu=np.full(C, s0["nu"]))
+    init = start_state(ref, C)
     ns = _native(ref, C, path)
     ns.set_state(**init)
     ns.sweep(S, seed=99, sweep0=7)
@@ -424,7 +285,7 @@ def test_sharding_invariance(path):
         nh.set_state(**{k: v[h * C // 2:(h + 1) * C // 2] for k, v in init.items()})
         nh.sweep(S, seed=99, sweep0=7, chain0=h * C // 2)
         halves.append(nh.get_state())
-    for k in ("x", "b", "z", "alpha", "pout", "theta", "nu"):
+    for k in STATE_KEYS:
         np.testing.assert_array_equal(full[k], np.concatenate([h[k] for h in halves]))
 
 
@@ -433,13 +294,7 @@ def test_two_chains_per_simd_build_matches():
     build; it must give bitwise the chains of the uncapped build (two half launches)."""
     ref = load_ref("beta_prior")
     C, S = 2048, 8
-    s0 = sweep_state(ref, 0)
-    lo = np.array([p.pmin for p in ref["pta"].params])
-    hi = np.array([p.pmax for p in ref["pta"].params])
-    init = dict(x=np.random.default_rng(11).uniform(lo, hi, size=(C, len(lo))),
-                b=np.tile(s0["b"], (C, 1)), z=np.tile(s0["z"], (C, 1)),
-                alpha=np.tile(s0["alpha"], (C, 1)), pout=np.tile(s0["pout"], (C, 1)),
-                theta=np.full(C, s0["theta"]), nu=np.full(C, s0["nu"]))
+    init = start_state(ref, C, 11)
     ns = _native(ref, C, "persistent")
     ns.set_state(**init)
     rec = ns.alloc_records(S)
@@ -454,7 +309,7 @@ def test_two_chains_per_simd_build_matches():
         hrec = nh.alloc_records(S)
         nh.sweep(S, records=hrec, seed=21, sweep0=4, chain0=h * C // 2)
         half = nh.get_state()
-        for k in ("x", "b", "z", "alpha", "pout", "theta", "nu", "status"):
+        for k in STATE_KEYS + ("status",):
             np.testing.assert_array_equal(full[k][sl], half[k], err_msg=k)
         for k, v in hrec.items():
             np.testing.assert_array_equal(frec[k][sl], v.cpu().numpy(), err_msg=f"rec {k}")
@@ -466,13 +321,7 @@ def test_paths_agree_in_philox_mode():
     decisions (floating-point differences are ~1e-13, far from any decision threshold)."""
     ref = load_ref("beta_prior")
     C, S = 64, 6
-    s0 = sweep_state(ref, 0)
-    lo = np.array([p.pmin for p in ref["pta"].params])
-    hi = np.array([p.pmax for p in ref["pta"].params])
-    init = dict(x=np.random.default_rng(3).uniform(lo, hi, size=(C, len(lo))),
-                b=np.tile(s0["b"], (C, 1)), z=np.tile(s0["z"], (C, 1)),
-                alpha=np.tile(s0["alpha"], (C, 1)), pout=np.tile(s0["pout"], (C, 1)),
-                theta=np.full(C, s0["theta"]), nu=np.full(C, s0["nu"]))
+    init = start_state(ref, C, 3)
     out = {}
     for path in PATHS:
         ns = _native(ref, C, path)
@@ -485,7 +334,7 @@ def test_paths_agree_in_philox_mode():
         (a["nu"] == b["nu"])
     assert same.mean() >= 0.95, same.mean()
     for k in ("b", "alpha", "pout", "theta"):
-        r = _rel(b[k][same], a[k][same])
+        r = rel(b[k][same], a[k][same])
         assert np.all(r <= 1e-8), f"{k}: max rel {r.max():.3e}"
 
 

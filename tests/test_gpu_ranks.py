@@ -14,6 +14,8 @@ import sys
 
 import pytest
 
+import gpu_support  # noqa: F401  (importing it is the device gate)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -34,10 +36,6 @@ def _bench(*args):
 
 
 def test_two_ranks_equal_one_rank_with_all_chains():
-    pytest.importorskip("torch")
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
     two = _bench("--gpus", "2", "--chains", "128")
     one = _bench("--gpus", "1", "--chains", "256")
     assert two["n_gpus"] == 2 and two["shards"] == [[0, 128], [128, 256]]

@@ -10,17 +10,14 @@ import warnings
 import numpy as np
 import pytest
 
+import gpu_support  # noqa: F401  (importing it is the device gate)
 from golden_io import load_ref, sweep_state
 
+from gibbs_student_t_amd._abi import STATUS_ERRORS
+from gibbs_student_t_amd import Gibbs
+from oracle.gibbs_oracle import ChainState, Oracle, OutlierModel
+
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd._abi import STATUS_ERRORS, STATUS_FLOOR  # noqa: E402
-from gibbs_student_t_amd import Gibbs  # noqa: E402
-from oracle.gibbs_oracle import ChainState, Oracle, OutlierModel  # noqa: E402
 
 
 def _load_state(g, s):
@@ -185,8 +182,8 @@ def test_checkpoint_resume_is_bitwise(name, tmp_path):
 
 def test_checkpoint_refuses_stale_pairs_and_other_datasets(tmp_path):
     """A stage call after sample() advances the Philox counter past the sampled x: the
-    checkpoint would not resume the uninterrupted chain, so it is refused (ADVICE r4).  A
-    checkpoint loads only on the dataset it was taken on (VERDICT r4 weak #8)."""
+    checkpoint would not resume the uninterrupted chain, so it is refused.  A
+    checkpoint loads only on the dataset it was taken on."""
     ref = load_ref("beta_fixed")
     g = Gibbs(ref["pta"], **ref["kw"], nchains=2, seed=7)
     x = g.sample(ref["xs"], niter=5)

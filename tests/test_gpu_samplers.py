@@ -2,7 +2,7 @@
 
 The injected-variate parity tests feed Gamma and Beta *values* from the reference's tape
 (parity contract 3), so the Philox samplers themselves are checked here, by
-distribution (VERDICT r5, next-round item 1):
+distribution:
 
 * gamma_mt (Marsaglia-Tsang, a < 1 by the a + 1 boost; the theta stage) and gamma_mt_slots<4>
   (the alpha stage's interleaved copy, gibbs.py:239) for shapes 0.5 - 2 -- the lower tail
@@ -16,7 +16,9 @@ import numpy as np
 import pytest
 import scipy.stats
 
-torch = pytest.importorskip("torch")
+from gpu_support import torch
+from gibbs_student_t_amd.native import debug_variates
+
 pytestmark = pytest.mark.gpu
 
 EPS = (1e-2, 1e-3, 1e-4, 1e-5, 1e-6, 1e-7, 1e-8)
@@ -24,14 +26,7 @@ CHUNK = 1 << 23                # a multiple of 256 (gamma_slots draws 4 x 64 per
 NTAIL = 12 * CHUNK             # ~1e8 draws
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a HIP device")
-
-
 def _tail_counts(kind, a, seed):
-    from gibbs_student_t_amd.native import debug_variates
     eps = torch.tensor(EPS, dtype=torch.float64, device="cuda:0")
     cnt = torch.zeros(len(EPS), dtype=torch.float64, device="cuda:0")
     for call in range(NTAIL // CHUNK):
@@ -60,7 +55,6 @@ def test_gamma_lower_tail(kind, a):
 @pytest.mark.parametrize("kind", ["gamma", "gamma_slots"])
 @pytest.mark.parametrize("a", [0.5, 0.7, 1.0, 2.0, 40.0])
 def test_gamma_bulk(kind, a):
-    from gibbs_student_t_amd.native import debug_variates
     g = debug_variates(kind, a, 1 << 21, seed=77, call=int(10 * a)).cpu().numpy()
     p = scipy.stats.kstest(g, scipy.stats.gamma(a).cdf).pvalue
     assert p > 1e-3, (kind, a, p)
@@ -72,7 +66,6 @@ def test_gamma_bulk(kind, a):
 def test_theta_beta(a, b):
     """Beta(sum z + n m, n - sum z + n (1 - m)) as the theta stage draws it: J1713 (n = 130,
     m = 0.01) with 2 / 4 flagged TOAs, ecq-like shapes, and a symmetric case."""
-    from gibbs_student_t_amd.native import debug_variates
     x = debug_variates("beta", a, 2_000_000, b=b, seed=5, call=int(a * 100)).cpu().numpy()
     p = scipy.stats.kstest(x, scipy.stats.beta(a, b).cdf).pvalue
     assert p > 1e-3, (a, b, p)

@@ -7,18 +7,15 @@ the refit; <= 1e-12 of the residual scale)."""
 import numpy as np
 import pytest
 
+import gpu_support  # noqa: F401  (importing it is the device gate)
 from gibbs_student_t_amd import data
-from gibbs_student_t_amd.model import FYR, fourier_basis, svd_tm_basis
+from gibbs_student_t_amd.model import FYR, PTA, fourier_basis, svd_tm_basis
+from gibbs_student_t_amd.native import NativeSampler
 from gibbs_student_t_amd.simulate import pairs, simulate_batch
 from oracle import sim_oracle as so
+from support import j1713_epochs as _j1713, prior_box
 
 pytestmark = pytest.mark.gpu
-
-
-def _j1713():
-    raw = data.load_j1713_raw()
-    mjd = raw["mjd_int"].astype(np.float64) + raw["mjd_frac"]
-    return mjd * data.DAY_SEC, data.design_matrix(mjd, raw["par"], raw["fit"]), raw
 
 
 def _oracle(toas, M, d, **kw):
@@ -78,8 +75,6 @@ def test_shards_draw_the_same_datasets():
 def test_large_batch_and_pairs_feed_the_sampler():
     """256 datasets (config 4's grid size) in one launch; the pairs run through the
     sampler's model setup and a few sweeps with finite state."""
-    from gibbs_student_t_amd.model import PTA
-    from gibbs_student_t_amd.native import NativeSampler
     toas, M, raw = _j1713()
     sim = simulate_batch(toas, M, 256, seed=1, theta=np.repeat([0.05, 0.1, 0.15, 0.2], 64))
     assert sim["residuals"].shape == (256, len(toas))
@@ -90,8 +85,7 @@ def test_large_batch_and_pairs_feed_the_sampler():
     ns = NativeSampler(ptas, cfg, 0)
     C = 64
     ns.alloc(C, dataset=np.repeat(np.arange(4), C // 4))
-    lo = np.array([p.pmin for p in ptas[0].params])
-    hi = np.array([p.pmax for p in ptas[0].params])
+    lo, hi = prior_box(ptas[0])
     ns.set_state(x=np.random.default_rng(0).uniform(lo, hi, size=(C, len(lo))),
                  theta=np.full(C, 0.05), nu=np.full(C, 4.0))
     ns.sweep(10, seed=3)

@@ -4,14 +4,11 @@ import os
 import numpy as np
 import pytest
 
+import gpu_support  # noqa: F401  (importing it is the device gate)
+from gibbs_student_t_amd import run_sims
+from gibbs_student_t_amd.native import NativeSampler
+
 pytestmark = pytest.mark.gpu
-
-torch = pytest.importorskip("torch")
-if not torch.cuda.is_available():  # pragma: no cover
-    pytest.skip("needs a HIP device", allow_module_level=True)
-
-from gibbs_student_t_amd import run_sims  # noqa: E402
-from gibbs_student_t_amd.native import NativeSampler  # noqa: E402
 
 
 @pytest.mark.parametrize("generator", ["host", "device"])

@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 
 from gibbs_student_t_amd import _abi, data, model
-from golden_io import CHAIN_KEYS, load_dataset
-import mgp_io
-import test_pack as tp
+from golden_io import (CHAIN_KEYS, GOLDEN, MGP_DATASETS, MGP_NAMES, fixture_names, load_dataset,
+                       load_ref)
+from support import PACKINGS, PACK_DIMS, host_tool, pack_dataset, run_packer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAND = np.linspace(1150.0, 1850.0, 3)
@@ -115,7 +115,7 @@ def test_defaults_are_todays_object(ds):
     """Without dm_gp / chrom_gp: one process over the whole Fourier block, T, Ffreqs, the
     parameters and phi bit for bit what the stored datasets hold."""
     pta = load_dataset(dataset=ds)
-    d = np.load(os.path.join(mgp_io.GOLDEN, f"{ds}_dataset.npz"))
+    d = np.load(os.path.join(GOLDEN, f"{ds}_dataset.npz"))
     # (golden_io names every single-backend pulsar J1713+0747)
     assert [n.split("_", 1)[1] for n in pta.param_names] == \
         [str(v).split("_", 1)[1] for v in d["names"]]
@@ -144,7 +144,7 @@ def test_constructor_defaults_bitwise():
     np.testing.assert_array_equal(a.T[:, :34], np.hstack([F, U]))
     np.testing.assert_array_equal(a.Ffreqs, ff)
     assert a.nfourier == 20 and a.m == 34 + a.n_ecorr and raw.freqs is None
-    d = np.load(os.path.join(mgp_io.GOLDEN, "ecb_dataset.npz"))
+    d = np.load(os.path.join(GOLDEN, "ecb_dataset.npz"))
     assert a.param_names == [str(v) for v in d["names"]]
     np.testing.assert_array_equal(a.T[:, 34:], d["T"][:, 34:])
     np.testing.assert_allclose(a.T[:, :20], d["T"][:, :20], rtol=0, atol=1e-12)
@@ -156,7 +156,7 @@ def test_multiband_new_arguments():
     """band_mhz / dm None: today's arrays (the mb and mid datasets' stored residuals); band_mhz
     alone changes nothing but freqs; dm adds a nu^-2 realisation from a generator of its own."""
     for ds, kw in (("mb", {}), ("mid", dict(nepochs=130, nsub=3, seed=390))):
-        d = np.load(os.path.join(mgp_io.GOLDEN, f"{ds}_dataset.npz"))
+        d = np.load(os.path.join(GOLDEN, f"{ds}_dataset.npz"))
         a = data.multiband(**kw)
         # the generator's stream is undisturbed: the error bars (its first draws) bit for bit,
         # the residuals (every later draw, then a projection) to the rounding of a projection
@@ -190,45 +190,25 @@ PACK_KEYS = ("Tmf", "Tcol", "resid", "sig2", "ref2int", "cidx", "csig2", "ccount
 
 
 def _pack(pack_bin, tmp_path, d, procs, packing="large"):
-    """tests/test_pack.py's descriptor file with the gst_model_procs arrays appended."""
-    MT, ntm_pad, raug = tp.PACKINGS[packing]
-    disjoint = 1
-    head = np.array([tp.N, tp.M, tp.NF, tp.NTM, tp.NEC, tp.NB, tp.P, 4, 4, ntm_pad, raug, MT,
-                     disjoint, 6, 7, 0 if procs is None else procs[0]], np.int32)
-    src, dst = tmp_path / "desc.bin", tmp_path / "packed.bin"
-    with open(src, "wb") as f:
-        f.write(head.tobytes())
-        for k in ("T", "residuals", "toaerrs", "ffreqs", "pmin", "pmax", "df_A", "df_B"):
-            f.write(np.ascontiguousarray(d[k], np.float64).tobytes())
-        for k in ("backend", "ecorr_backend", "ecorr_idx", "efac_idx", "equad_idx", "hyper_idx",
-                  "white_idx"):
-            f.write(np.ascontiguousarray(d[k], np.int32).tobytes())
-        if procs is not None:
-            f.write(np.array(procs[1] + procs[2] + procs[3], np.int32).tobytes())
-    subprocess.run([pack_bin, str(src), str(dst)], check=True)
-    out, raw, pos = {}, dst.read_bytes(), 0
-    while pos < len(raw):
-        end = raw.index(b"\n", pos)
-        name, dtype, count = raw[pos:end].decode().split()
-        size = int(count) * int(dtype[1])
-        out[name] = np.frombuffer(raw[end + 1:end + 1 + size], dtype="<" + dtype)
-        pos = end + 1 + size
-    return out
+    MT, ntm_pad, raug = PACKINGS[packing]
+    return run_packer(pack_bin, tmp_path, d, MT, ntm_pad, raug, 1, procs)
 
 
-pack_bin = tp.pack_bin
+@pytest.fixture(scope="module")
+def pack_bin(tmp_path_factory):
+    return host_tool(tmp_path_factory, "pack_dump")
 
 
 @pytest.mark.parametrize("packing", ["large", "gen"])
 def test_pack_one_process_is_todays_packed_model(pack_bin, tmp_path, packing):
-    d = tp.dataset("classes")
+    d = pack_dataset("classes")
     legacy = _pack(pack_bin, tmp_path, d, None, packing)
-    one = _pack(pack_bin, tmp_path, d, (1, [tp.NF, 0, 0], [6, 0, 0], [7, 0, 0]), packing)
+    one = _pack(pack_bin, tmp_path, d, (1, [PACK_DIMS[1], 0, 0], [6, 0, 0], [7, 0, 0]), packing)
     assert set(legacy) == set(one)
     for k in legacy:
         assert legacy[k].tobytes() == one[k].tobytes(), k
     assert set(PACK_KEYS) <= set(legacy)
-    assert one["nproc"][0] == 1 and one["pcol"].tolist() == [0, tp.NF, tp.NF, tp.NF]
+    assert one["nproc"][0] == 1 and one["pcol"].tolist() == [0, PACK_DIMS[1], PACK_DIMS[1], PACK_DIMS[1]]
     assert one["pidxA"].tolist() == [6, 6, 6] and one["pidxG"].tolist() == [7, 7, 7]
     # one process: its sums are the block's, the values today's loop gives
     f = d["ffreqs"]
@@ -241,7 +221,7 @@ def test_pack_one_process_is_todays_packed_model(pack_bin, tmp_path, packing):
 def test_pack_log_df_restarts_at_a_process_boundary(pack_bin, tmp_path):
     """Two processes of one pair each over the 4 Fourier columns, both ladders starting at f_1:
     the legacy packer forms log(f_1 - f_1) at the boundary; with the layout df restarts."""
-    d = tp.dataset("classes")
+    d = pack_dataset("classes")
     f1 = 1.0 / 3e8
     d["ffreqs"] = np.repeat([f1, f1], 2)
     with np.errstate(divide="ignore"):
@@ -302,10 +282,10 @@ def test_model_procs_struct_layout(tmp_path):
 
 
 # ---- the fixtures and the oracle --------------------------------------------------------------
-@pytest.mark.parametrize("ds", list(mgp_io.DATASETS))
+@pytest.mark.parametrize("ds", list(MGP_DATASETS))
 def test_fixture_layout(ds):
-    pta = mgp_io.load_dataset(ds)
-    ncols, nec, path = mgp_io.DATASETS[ds]
+    pta = load_dataset(dataset=ds)
+    ncols, nec, path = MGP_DATASETS[ds]
     assert tuple(q.ncol for q in pta.procs) == ncols and pta.n_ecorr == nec
     assert [q.name for q in pta.procs] == ["red", "dm_gp", "chrom_gp"][:len(ncols)]
     assert pta.nfourier == sum(ncols) and pta.m == sum(ncols) + pta.ntm + nec
@@ -313,19 +293,18 @@ def test_fixture_layout(ds):
         assert len(pta.params) <= 8 and sum(ncols) + nec <= 46 and pta.ntm <= 16
     else:
         assert sum(ncols) + nec > 60
-    for kind in mgp_io.KINDS:
-        fn = os.path.join(mgp_io.GOLDEN, f"mgp_ref_{ds}_beta_{kind}.npz")
+    for kind in ("fixed", "prior"):
+        fn = os.path.join(GOLDEN, f"mgp_ref_{ds}_beta_{kind}.npz")
         assert os.path.getsize(fn) <= 392975       # ref_wide_beta_fixed.npz, today's largest
-    from golden_io import fixture_names
     assert not any(n.startswith(("dm", "mgp")) for n in fixture_names())
 
 
-@pytest.mark.parametrize("name", mgp_io.NAMES)
+@pytest.mark.parametrize("name", MGP_NAMES)
 def test_legacy_stream_reproduces_reference_bit_exact(name):
     """The unchanged oracle on the reference's RNG stream: identical chains, and the recorded
     sweep count (12; dm3: 6) from the injected values and from a prior draw."""
     from oracle.gibbs_oracle import Oracle, OutlierModel
-    ref = mgp_io.load_ref(name)
+    ref = load_ref(name)
     assert int(ref["niter"]) == (6 if name.startswith("dm3") else 12)
     assert int(ref["prior_draw"]) == int(name.endswith("prior"))
     orc = Oracle(ref["pta"], OutlierModel(**ref["kw"]))

@@ -137,7 +137,7 @@ def test_floor_gate_only_where_the_reference_floors():
     the exact mean cho_solve(Sigma, d) is closer to the reference's own SVD mean than the
     floor mean (round 4's 1e-14 gate) would be on most sweeps and in total -- e.g.
     vvh17_fixed sweeps 0-5, where LAPACK still resolves the eigenvalues: exact ~1e-6, floor
-    2e-2..2e-1 from the reference (VERDICT r4 weak #1)."""
+    2e-2..2e-1 from the reference."""
     import scipy.linalg as sl
     closer = farther = 0
     e_exact = e_floor = 0.0

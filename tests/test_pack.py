@@ -2,79 +2,20 @@
 tools/pack_dump.cpp as the large path and as a persistent GEN shape does, compared exactly
 with a numpy restatement of the layouts documented on DevModel (csrc/gst_model.h)."""
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N, NF, NTM, NEC, NB, P = 70, 4, 3, 18, 2, 8
+from support import PACKINGS, PACK_DIMS, host_tool, pack_dataset as dataset, run_packer
+
+N, NF, NTM, NEC, NB, P = PACK_DIMS
 M = NF + NTM + NEC
 NPAD, NKS = 128, 18                      # 70 TOAs: two 64-TOA slots, 18 k-steps of 4
-# (MT, ntm_pad, raug): the large path (mp = 48) and the GEN shape (8, 2, 62) (mp = 64)
-PACKINGS = {"large": (0, 16, 38), "gen": (8, 16, 62)}
 
 
 @pytest.fixture(scope="module")
 def pack_bin(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = tmp_path_factory.mktemp("pack") / "pack_dump"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "gibbs_student_t_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "pack_dump.cpp"), "-o", str(out)], check=True)
-    return str(out)
-
-
-def dataset(variant):
-    """classes: <= 8 (sigma, backend) classes; sigmas: 9 distinct sigmas; overlap: one TOA in
-    two epochs"""
-    rng = np.random.default_rng(11)
-    T = np.zeros((N, M))
-    T[:, :NF + NTM] = rng.standard_normal((N, NF + NTM))
-    # 18 epochs of 1..5 TOAs (51 TOAs), scattered; the other 19 TOAs are in no epoch
-    sizes = [1 + e % 5 for e in range(NEC)]
-    toas = rng.permutation(N)[:sum(sizes)]
-    start = np.concatenate([[0], np.cumsum(sizes)])
-    for e in range(NEC):
-        T[toas[start[e]:start[e + 1]], NF + NTM + e] = 0.5 + rng.random(sizes[e])
-    if variant == "overlap":
-        T[toas[0], NF + NTM + 7] = 0.25      # epoch 0's TOA also in epoch 7
-    backend = rng.integers(0, NB, N).astype(np.int32)
-    nsig = 9 if variant == "sigmas" else 3
-    toaerrs = (1e-7 * (1 + np.arange(nsig)))[rng.integers(0, nsig, N)]
-    if variant == "sigmas":
-        toaerrs[:9] = 1e-7 * (1 + np.arange(9))
-    return dict(T=T, residuals=1e-6 * rng.standard_normal(N), toaerrs=toaerrs,
-                ffreqs=np.repeat(np.array([1.0, 2.0]) / 3e8, 2), pmin=-np.arange(1.0, P + 1),
-                pmax=np.arange(2.0, P + 2) / 3, df_A=rng.random(30), df_B=rng.random(30),
-                backend=backend, ecorr_backend=rng.integers(0, NB, NEC).astype(np.int32),
-                ecorr_idx=np.array([4, 5], np.int32), efac_idx=np.array([0, 1], np.int32),
-                equad_idx=np.array([2, 3], np.int32), hyper_idx=np.array([4, 5, 6, 7], np.int32),
-                white_idx=np.array([0, 1, 2, 3], np.int32))
-
-
-def pack(pack_bin, tmp_path, d, MT, ntm_pad, raug, disjoint):
-    head = np.array([N, M, NF, NTM, NEC, NB, P, 4, 4, ntm_pad, raug, MT, disjoint, 6, 7, 0], np.int32)
-    src, dst = tmp_path / "desc.bin", tmp_path / "packed.bin"
-    with open(src, "wb") as f:
-        f.write(head.tobytes())
-        for k in ("T", "residuals", "toaerrs", "ffreqs", "pmin", "pmax", "df_A", "df_B"):
-            f.write(np.ascontiguousarray(d[k], np.float64).tobytes())
-        for k in ("backend", "ecorr_backend", "ecorr_idx", "efac_idx", "equad_idx", "hyper_idx",
-                  "white_idx"):
-            f.write(np.ascontiguousarray(d[k], np.int32).tobytes())
-    subprocess.run([pack_bin, str(src), str(dst)], check=True)
-    out, raw, pos = {}, dst.read_bytes(), 0
-    while pos < len(raw):
-        end = raw.index(b"\n", pos)
-        name, dtype, count = raw[pos:end].decode().split()
-        size = int(count) * int(dtype[1])
-        out[name] = np.frombuffer(raw[end + 1:end + 1 + size], dtype="<" + dtype)
-        pos = end + 1 + size
-    return out
+    return host_tool(tmp_path_factory, "pack_dump")
 
 
 def mfma_tiles(A):
@@ -170,7 +111,7 @@ def test_pack(pack_bin, tmp_path, variant, packing):
     MT, ntm_pad, raug = PACKINGS[packing]
     d = dataset(variant)
     want, mp = expected(d, MT, ntm_pad, raug)
-    got = pack(pack_bin, tmp_path, d, MT, ntm_pad, raug, int(want["disjoint"]))
+    got = run_packer(pack_bin, tmp_path, d, MT, ntm_pad, raug, int(want["disjoint"]))
     ints = dict(zip(("nks", "npad", "mp", "gx_nt", "nkse", "neblk", "ncls", "ec_disjoint", "n", "m",
                      "nf", "ntm", "ntm_pad", "raug", "nslot_toa", "nec", "nb"), got["ints"]))
     assert ints == dict(nks=NKS, npad=NPAD, mp=mp, gx_nt=want["gx_nt"], nkse=want["nkse"],

@@ -2,13 +2,12 @@
 which order and shape, the LDS layouts' totals and the persistent kernel's launch shape.  The
 expected lists are written by hand from the class rules at the head of gst_plan.h (white /
 toa / hyper classes, ec_reg_mt, gram_ec_of); tools/plan_dump.cpp prints the planner's."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import host_tool
+
 ALL = 0x7F
 GRAM_ONLY = 0x100                      # GST_STAGE_GRAM
 D_GRAM, D_HYPER, D_EXACT, D_EPOCHS = 2, 4, 8, 32   # GST_DEBUG_LARGE_GRAM, ...
@@ -17,13 +16,7 @@ GRAM_LDS = (2 * 16 * 8 * 64 + 2 * 8 * 64) * 8
 
 @pytest.fixture(scope="module")
 def plan_bin(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = tmp_path_factory.mktemp("plan") / "plan_dump"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "gibbs_student_t_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "plan_dump.cpp"), "-o", str(out)], check=True)
-    return str(out)
+    return host_tool(tmp_path_factory, "plan_dump")
 
 
 def r16(a):

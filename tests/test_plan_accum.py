@@ -1,25 +1,18 @@
 """The launch planner with the posterior sums on (plan_large's acc_on, csrc/gst_plan.h): the
 sweep list gains lg_accum directly after lg_record's place, one workgroup per chain, and
 nothing else changes; without it the lists are the planner's usual ones."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import host_tool
+
 ALL = 0x7F
 
 
 @pytest.fixture(scope="module")
 def plan_bin(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    out = tmp_path_factory.mktemp("plan") / "plan_dump"
-    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I",
-                    os.path.join(ROOT, "gibbs_student_t_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "plan_dump.cpp"), "-o", str(out)], check=True)
-    return str(out)
+    return host_tool(tmp_path_factory, "plan_dump")
 
 
 def r16(a):

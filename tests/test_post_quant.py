@@ -3,7 +3,6 @@ the notebook's median rule np.median(poutchain, axis=0) > tau decided exactly fr
 with the one undecidable case reported, never guessed -- and the mean and spread of the
 signal T b at every TOA from the sums of y = r - T b and y^2.  Host arithmetic only."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch.multiprocessing as mp
 
 from gibbs_student_t_amd import dist
 from gibbs_student_t_amd.post import PosteriorSums
+from support import free_port
 
 THR = (0.2, 0.5, 0.9)
 N, M = 11, 4
@@ -167,14 +167,6 @@ def test_merging_and_files(tmp_path):
 C2, S2 = 3, 31
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _rank_data(rank):
     b, T, r = _signal(C2, S2, 12)
     b = b + np.random.default_rng([3, rank]).normal(size=b.shape)
@@ -198,7 +190,7 @@ def _worker(rank, world, port, out):
 def test_two_rank_pooling_of_counts_and_band():
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -4,6 +4,7 @@ import os
 import numpy as np
 
 from gibbs_student_t_amd import run_sims
+from support import prior_box
 
 
 def test_grid_matches_run_sims_structure():
@@ -42,7 +43,6 @@ def test_initial_state_per_model():
         assert np.all(s["z"][:, :n] == z0) and np.all(s["z"][:, n:] == 0)
         a0 = 1e10 if x.model == "vvh17" else 1.0                           # gibbs.py:44-47
         assert np.all(s["alpha"][:, :n] == a0)
-        lo = np.array([p.pmin for p in x.pta.params])
-        hi = np.array([p.pmax for p in x.pta.params])
+        lo, hi = prior_box(x.pta)
         assert np.all((s["x"] >= lo) & (s["x"] <= hi))
         assert s["theta"][0] == 0.01 and s["nu"][0] == 4.0

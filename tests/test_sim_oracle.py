@@ -7,7 +7,7 @@ from oracle import sim_oracle as so
 from gibbs_student_t_amd import data
 from gibbs_student_t_amd.model import FYR, fourier_basis, svd_tm_basis
 
-from test_philox import KAT
+from support import KAT, j1713_epochs as _j1713
 
 
 @pytest.mark.parametrize("ctr,key,want", KAT)
@@ -16,14 +16,6 @@ def test_numpy_philox_known_answers(ctr, key, want):
     k = [int(x, 16) for x in key.split()]
     out = so.philox(*c, *k)
     assert " ".join(f"{int(v):08x}" for v in out) == want
-
-
-def _j1713():
-    raw = data.load_j1713_raw()
-    mjd = raw["mjd_int"].astype(np.float64) + raw["mjd_frac"]
-    toas = mjd * data.DAY_SEC
-    M = data.design_matrix(mjd, raw["par"], raw["fit"])
-    return toas, M, raw
 
 
 def test_recipe_properties():

@@ -13,14 +13,23 @@ import numpy as np
 
 sys.path.insert(0, ".")
 sys.path.insert(0, "tests")
-from test_gpu_waves import KEYS, _init, _run  # noqa: E402
+from gpu_support import open_sampler, run_sweeps  # noqa: E402
+from gibbs_student_t_amd.native import STATE_KEYS as KEYS  # noqa: E402
 from golden_io import load_ref  # noqa: E402
+from support import start_state  # noqa: E402
+
+
+def _run(ref, C, S, waves, init, mask=0x7F, seed=7, sweep0=3, chain0=0):
+    ns = open_sampler(ref, C, "persistent", waves)
+    ns.set_state(**init)
+    return run_sweeps(ns, S, seed=seed, sweep0=sweep0, mask=mask, chain0=chain0)
+
 
 name = sys.argv[1] if len(sys.argv) > 1 else "beta_efac_fixed"
 ref = load_ref(name)
 C, S = int(os.environ.get("WD_C", 96)), int(os.environ.get("WD_S", 24))
 SWEEP0, SEED = 3, 7
-init = _init(ref, C, 5)
+init = start_state(ref, C, 5)
 one, r1 = _run(ref, C, S, 1, init, seed=SEED, sweep0=SWEEP0)
 two, r2 = _run(ref, C, S, 2, init, seed=SEED, sweep0=SWEEP0)
 first = {}

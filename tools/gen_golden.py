@@ -575,7 +575,7 @@ def multi_gp_model(tag):
 def multi_gp(only=None):
     """``mgp_<ds>_dataset.npz`` and ``mgp_ref_<ds>_beta_{fixed,prior}.npz``: 12 recorded sweeps
     (dm3: 6) of the reference from the injected values and from a prior draw.  (Not
-    ``ref_*.npz``: golden_io.fixture_names globs that pattern; tests/mgp_io.py loads these.)"""
+    ``ref_*.npz``: golden_io.fixture_names globs that pattern; golden_io.load_ref finds these by their dataset prefix.)"""
     for j, tag in enumerate(MGP_DATASETS):
         if only and tag not in only:
             continue

@@ -24,7 +24,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from bench import CFG, initial_state  # noqa: E402
 from golden_io import load_dataset  # noqa: E402
-import mgp_io  # noqa: E402
 from gibbs_student_t_amd.native import NativeSampler  # noqa: E402
 
 
@@ -56,7 +55,7 @@ def main():
     names = (sys.argv[2] if len(sys.argv) > 2 else "ecb,ecq,jb").split(",")
     out = []
     for nm in names:
-        pta = mgp_io.load_dataset(nm) if nm in mgp_io.DATASETS else load_dataset(dataset=nm)
+        pta = load_dataset(dataset=nm)
         for C in [int(v) for v in os.environ.get("GR_CHAINS", "512,2048").split(",")]:
             for path in os.environ.get("GR_PATHS", "persistent,large").split(","):
                 r, ok, stages = rate(pta, path, C, S)

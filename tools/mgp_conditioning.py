@@ -17,8 +17,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from mgp_io import NAMES, load_ref  # noqa: E402
-from golden_io import sweep_state  # noqa: E402
+from golden_io import MGP_NAMES as NAMES, load_ref, sweep_state  # noqa: E402
 from oracle.gibbs_oracle import ChainState, lnlike_marginal_extended  # noqa: E402
 
 RTOL = 1e-10

@@ -34,14 +34,12 @@ SEED = 424242
 
 def load_model(dataset):
     """(pta, fixture prefix): the golden datasets, and the multi-process ones (red noise + DM
-    (+ chromatic), tests/mgp_io.py), whose fixtures are named mgp_samestart_*."""
+    (+ chromatic), golden_io.MGP_DATASETS), whose fixtures are named mgp_samestart_*."""
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import mgp_io
-    if dataset in mgp_io.DATASETS:
-        return mgp_io.load_dataset(dataset), "mgp_samestart"
-    from golden_io import load_dataset
-    return load_dataset(dataset=dataset), "samestart"
+    from golden_io import MGP_DATASETS, load_dataset
+    return load_dataset(dataset=dataset), \
+        "mgp_samestart" if dataset in MGP_DATASETS else "samestart"
 
 
 def start(pta, c):
