@@ -77,7 +77,9 @@ __device__ __forceinline__ double floor_shift(const double (&apr)[2], int lane, 
 // registers (the column-side mask zeroes every later update to it), so chol_harvest reads
 // both from L after the elimination; chol_stats then gives sum log a_kk (= log|Sigma| over
 // these columns, as mantissa product + exponent sum), sum a_{raug,k}^2 / a_kk (= the
-// d^T Sigma^-1 d contribution) and the failure flag.
+// d^T Sigma^-1 d contribution) and the failure flag.  The hyper MH's likelihoods take the same
+// statistics straight from the diagonal lanes (chol_stats_diag) and harvest once per sweep,
+// in front of the b draw.
 struct CholCtx {
   double* colq;   // [8][MT] the published column (paired tail: the even column, [8][PW])
   double* junk;   // [8][MT] where the other lanes' publishing stores land (see chol_publish)
@@ -432,6 +434,60 @@ __device__ __forceinline__ void chol_stats(CholCtx& cc) {
   cc.mant = (rdlane(mm, 0) * rdlane(mm, 16)) * (rdlane(mm, 32) * rdlane(mm, 48));
   cc.expo = wave_sum_i(ee);
   cc.quad = wave_sum(qd);
+  cc.fail = __ballot(f) != 0ull ? 1 : 0;
+}
+
+// The same three statistics of an elimination over columns [KLO, KEND = RA) read where the
+// elimination leaves them, with no harvest in front (the hyper MH's likelihoods: an MH step
+// needs only these wave-uniform numbers, the gathered pivots and entries only the b draw).
+//  * The pivot of column 8K + q is frozen in slot (K, K) of the diagonal lane 9q: each diagonal
+//    lane multiplies the mantissas and adds the exponents of its own residue class over the
+//    slot columns, then chol_stats' product and sum over the lanes combine the eight classes.
+//    An entry outside the range counts as mantissa 1, exponent 0 (only the last slot column can
+//    hold one), and so does every other lane: selects, no exec-masked region.  A dummy pad
+//    column (pivot 1) gives mantissa 1/2, exponent 1 as in chol_stats: exact.
+//  * The failure flag is !(a > 0) of the in-range pivots on the diagonal lanes (NaN fails).
+//  * The augmented row's own diagonal element, slot (RA / 8, RA / 8) of lane 9 (RA % 8), has
+//    received -= a_{RA,k}^2 / a_kk at every step: s0rr (its value before the elimination) minus
+//    what it holds now is sum a_{RA,k}^2 / a_kk.  No prior is added to that element.
+// The sums differ from chol_stats' in their last bits (another order of the same terms; the
+// quadratic form by one subtraction of two accumulated numbers: tests/test_hyper_diag_stats_cpu.py
+// bounds both against a long-double elimination).
+template <int MT, int KLO, int KEND, int RA>
+__device__ __forceinline__ void chol_stats_diag(const double (&L)[SL(MT, 0)], CholCtx& cc,
+                                                double s0rr) {
+  static_assert(KEND == RA && RA < 8 * MT, "the corner follows the last eliminated column");
+  static_assert(KLO % 8 == 0 && KLO < KEND, "the range starts at a slot column");
+  constexpr int R = RA / 8, PA = RA % 8;
+  const bool dg = cc.p == cc.q;
+  double mm = 1.0;
+  int ee = 0, f = 0;
+#pragma unroll
+  for (int K = KLO / 8; K <= (KEND - 1) / 8; ++K) {
+    const double a = L[SL(K, K)];
+    int e;
+    double mk = frexp(a, &e);
+    int fk = !(a > 0.0) ? 1 : 0;
+    if (8 * K + 8 > KEND) {   // the partial last slot column
+      const bool in = cc.q < KEND - 8 * K;
+      mk = in ? mk : 1.0;
+      e = in ? e : 0;
+      fk = in ? fk : 0;
+    }
+    mm *= mk;
+    ee += e;
+    f |= fk;
+  }
+  mm = dg ? mm : 1.0;
+  ee = dg ? ee : 0;
+  f = dg ? f : 0;
+  mm *= dpp<DPP_XOR1>(mm);
+  mm *= dpp<DPP_XOR2>(mm);
+  mm *= dpp<DPP_ROR4>(mm);
+  mm *= dpp<DPP_ROR8>(mm);
+  cc.mant = (rdlane(mm, 0) * rdlane(mm, 16)) * (rdlane(mm, 32) * rdlane(mm, 48));
+  cc.expo = wave_sum_i(ee);
+  cc.quad = s0rr - rdlane(L[SL(R, R)], 9 * PA);
   cc.fail = __ballot(f) != 0ull ? 1 : 0;
 }
 

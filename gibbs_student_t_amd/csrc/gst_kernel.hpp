@@ -926,17 +926,17 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     for (int r = K0; r < MT; ++r) asm("" : "+v"(phd[r - K0]));
 #pragma unroll
     for (int r = K0; r < MT; ++r) L[SL(r, r)] = (p == q) ? L[SL(r, r)] + phd[r - K0] : L[SL(r, r)];
-    CholCtx cc{colq, phbuf, colq2, lane, p, q, raug, 1.0, 0.0, 0, 0, {tm_apr, 1.0}, {tm_zr, 0.0}};
+    CholCtx cc{colq, phbuf, colq2, lane, p, q, raug, 1.0, 0.0, 0, 0, {1.0, 1.0}, {0.0, 0.0}};
     GST_SUB_END(7)
     chol_range<MT, K0, RA, kp_for(OCC)>(L, cc);
     GST_SUB_END(8)
-    chol_harvest<MT, 8 * K0, RA, RA>(L, cc);
-    chol_stats<8 * K0, RA>(cc);
+    // the statistics where the elimination left them (no harvest: harvest_factor, once per
+    // sweep).  The augmented row's diagonal element before the elimination comes from S0 again,
+    // through the lane's own S0 address: held in a register across the elimination it would
+    // add to the spill of the two-chains-per-SIMD build
+    chol_stats_diag<MT, 8 * K0, RA, RA>(
+        L, cc, rdlane(S0[64 * SL(RA / 8 - K0, RA / 8 - K0)], 9 * (RA % 8)));
     GST_SUB_END(19)
-    f_apr[0] = cc.apr[0];
-    f_apr[1] = cc.apr[1];
-    f_zr[0] = cc.zr[0];
-    f_zr[1] = cc.zr[1];
     const double mant = cc.mant, quad = cc.quad;
     const int expo = cc.expo;
     failed = cc.fail | fail_tm;
@@ -944,6 +944,17 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
     // log|Sigma| = sum log a_kk (pivots of the LDL^T-scaled elimination)
     const double ld_sigma = log(ld_tm_m * mant) + (double)(ld_tm_e + expo) * LN2;
     return marginal_ll(logdetN, rNr, quad_tm + quad, ld_sigma, logdet_phi);
+  };
+  // The pivots and augmented-row entries of the factor lnl_hyper left in L, gathered onto
+  // lane k % 64 behind the timing-model columns' for floor_shift and the b draw: once per
+  // sweep (and floor pass) at the final x, where they are consumed, not per likelihood
+  auto harvest_factor = [&]() __attribute__((always_inline)) {
+    CholCtx cc{colq, phbuf, colq2, lane, p, q, raug, 1.0, 0.0, 0, 0, {tm_apr, 1.0}, {tm_zr, 0.0}};
+    chol_harvest<MT, 8 * K0, RA, RA>(L, cc);
+    f_apr[0] = cc.apr[0];
+    f_apr[1] = cc.apr[1];
+    f_zr[0] = cc.zr[0];
+    f_zr[1] = cc.zr[1];
   };
 
   // pair mode: both waves write the records (identical state): b and the TOA slots split
@@ -1363,6 +1374,7 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
             }
           }
         }
+        if (redraw && !fb && role == owner) harvest_factor();
         if (pass == 1 || !redraw || fb || (st.debug & DEBUG_EXACT_BDRAW)) break;
         // the owner wave holds the factor at the final x; both waves take its floor decision
         const double fs =
@@ -1460,6 +1472,8 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
         }
         GST_SUB_END(26)
       }
+      // the factor in L is the accepted last step's or step NHYPER's: at the final x
+      if (!eval_only && redraw && !fb) harvest_factor();
       if (pass == 1 || eval_only || !redraw || fb || (st.debug & DEBUG_EXACT_BDRAW)) break;
       fshift = floor_shift(f_apr, lane, md.ntm, md.ntm_pad, md.ntm_pad + md.nf + (GEN ? md.nec : 0));
       if (__builtin_expect(fshift == 0.0, 1)) break;
