@@ -48,12 +48,12 @@ EXPORTS = ("gst_version", "gst_tape_stride", "gst_last_error", "gst_ctx_create",
            # ABI 7
            "gst_set_accum",
            # additive to ABI 7: found by symbol lookup
-           "gst_set_accum_toa", "gst_model_set_procs")
+           "gst_set_accum_toa", "gst_model_set_procs", "gst_set_accum_block")
 
 # entry points that older builds (A/B timing of library variants) may lack; calling one on
 # such a build raises AttributeError
 OPTIONAL = ("gst_set_debug", "gst_gram_counts", "gst_debug_variates", "gst_set_accum",
-            "gst_set_accum_toa", "gst_model_set_procs")
+            "gst_set_accum_toa", "gst_model_set_procs", "gst_set_accum_block")
 
 _P = ct.POINTER
 _D = _P(ct.c_double)
@@ -116,6 +116,14 @@ class AccumToa(ct.Structure):
     """gst_accum_toa: per-TOA exceedance counts of pout and the sums of y = r - T b."""
     _fields_ = [("nthr", ct.c_int), ("thr", ct.c_double * 4), ("pout_gt", ct.c_void_p),
                 ("resid_sum", ct.c_void_p), ("resid_sq", ct.c_void_p)]
+
+
+BLOCK_MAX = 256   # GST_BLOCK_MAX
+
+
+class AccumBlock(ct.Structure):
+    """gst_accum_block: packed lower triangle of sum b b^T over columns [col0, col0 + ncol)."""
+    _fields_ = [("col0", ct.c_int), ("ncol", ct.c_int), ("bb", ct.c_void_p)]
 
 
 class Tape(ct.Structure):
@@ -181,6 +189,8 @@ def load(path: str | None = None):
         lib.gst_set_accum.argtypes = [ct.c_void_p, _P(Accum)]
     if hasattr(lib, "gst_set_accum_toa"):
         lib.gst_set_accum_toa.argtypes = [ct.c_void_p, _P(AccumToa)]
+    if hasattr(lib, "gst_set_accum_block"):
+        lib.gst_set_accum_block.argtypes = [ct.c_void_p, _P(AccumBlock)]
     lib.gst_set_path.argtypes = [ct.c_void_p, ct.c_int]
     lib.gst_get_path.argtypes = [ct.c_void_p, _P(ct.c_int)]
     lib.gst_set_waves.argtypes = [ct.c_void_p, ct.c_int]

@@ -63,6 +63,8 @@ struct Ctx {
   // copy) and the chain count its plane stride was last written for
   gst_accum_toa acc_toa{};
   int acc_C = 0;
+  // gst_set_accum_block: the caller's descriptor (zero when unset; same device copy)
+  gst_accum_block acc_blk{};
   std::vector<void*> allocs;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -451,6 +453,9 @@ static int model_set(void* ctx, const gst_model_desc* descs, const gst_model_pro
     if (hc == 2) HIP_OK(set_lds((const void*)gst::lg_hyper<2>, lds_h2));
   }
   cx->has_model = true;
+  // a block's column range belongs to the model it was checked against
+  cx->acc_blk = gst_accum_block{};
+  cx->acc_dirty = cx->acc_on;
   return 0;
 }
 
@@ -617,12 +622,14 @@ static int launch(Ctx* cx, const gst_state* s, const gst_records* r, const gst_t
   if (acc_on && (cx->acc_dirty || (cx->acc_toa.pout_gt && C != cx->acc_C))) {
     const gst_accum& h = cx->acc;
     const gst_accum_toa& t = cx->acc_toa;
+    const gst_accum_block& k = cx->acc_blk;
     hipLaunchKernelGGL(set_accum_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream,
                        gst::accum_desc(cx->gram_cnt),
                        gst::DevAccum{h.z_sum, h.pout_sum, h.alpha_sum, h.b_sum, h.b_sq, h.count,
                                      h.from_sweep, t.pout_gt, t.resid_sum, t.resid_sq,
                                      {t.thr[0], t.thr[1], t.thr[2], t.thr[3]},
-                                     (long long)C * cx->nmax, t.pout_gt ? t.nthr : 0});
+                                     (long long)C * cx->nmax, t.pout_gt ? t.nthr : 0,
+                                     k.col0, k.ncol, k.bb});
     HIP_OK(hipGetLastError());
     cx->acc_dirty = false;
     cx->acc_C = C;
@@ -699,6 +706,23 @@ int gst_set_accum_toa(void* ctx, const gst_accum_toa* a) {
   cx->acc_toa = a ? *a : gst_accum_toa{};
   if (cx->acc_toa.nthr == 0) cx->acc_toa.pout_gt = nullptr;
   for (int k = cx->acc_toa.nthr; k < 4; ++k) cx->acc_toa.thr[k] = 0.0;
+  cx->acc_dirty = cx->acc_on;
+  return 0;
+}
+
+int gst_set_accum_block(void* ctx, const gst_accum_block* blk) {
+  Ctx* cx = static_cast<Ctx*>(ctx);
+  if (!cx) return fail("gst_set_accum_block: null ctx");
+  if (blk) {
+    if (!cx->has_model) return fail("gst_set_accum_block: no model set");
+    if (blk->col0 < 0) return fail("gst_set_accum_block: col0 must be >= 0");
+    if (blk->ncol < 1 || blk->ncol > GST_BLOCK_MAX)
+      return fail("gst_set_accum_block: ncol must be 1.." + std::to_string(GST_BLOCK_MAX));
+    if (blk->col0 > cx->m - blk->ncol)
+      return fail("gst_set_accum_block: col0 + ncol exceeds the model's " +
+                  std::to_string(cx->m) + " columns");
+  }
+  cx->acc_blk = blk && blk->bb ? *blk : gst_accum_block{};
   cx->acc_dirty = cx->acc_on;
   return 0;
 }

@@ -1065,6 +1065,57 @@ __global__ void __launch_bounds__(64 * WPB, OCC)
         }
         if (lane == 0 && role == 0)
           if (long long* const cnt = A.count) cnt[c] += 1;
+        // gst_set_accum_block: the packed lower triangle of b b^T over the columns
+        // [bb_col0, bb_col0 + bb_ncol) of the state row.  Row i belongs to one wave (pair mode:
+        // role i & 1), element (i, j) to lane j & 63: a lane holds its one or two b_j for the
+        // whole pass (m <= MP <= 128) and reads the wave-uniform b_i from the owning lane.  The
+        // read-modify-writes of BBG rows are in flight together, one wait per group, and the
+        // group loop stays rolled: the instances are at the register limit.
+        if (double* const bo = A.bb) {
+          static_assert(MP <= 128, "a lane holds two columns of the block");
+          constexpr int BBG = 8;
+          constexpr int RSTEP = PAIR ? 2 : 1;
+          const int c0 = A.bb_col0, K = A.bb_ncol;
+          double* const tri = bo + (size_t)c * (size_t)(K * (K + 1) / 2);
+          const double bj0 = lane < K ? brow[c0 + lane] : 0.0;
+          const double bj1 = lane + 64 < K ? brow[c0 + 64 + lane] : 0.0;
+          // columns j = lane of every row
+#pragma unroll 1
+          for (int i0 = role; i0 < K; i0 += BBG * RSTEP) {
+            double v[BBG];
+#pragma unroll
+            for (int g = 0; g < BBG; ++g) {
+              const int i = i0 + g * RSTEP;
+              v[g] = (i < K && lane <= i) ? tri[i * (i + 1) / 2 + lane] : 0.0;
+            }
+#pragma unroll
+            for (int g = 0; g < BBG; ++g) {
+              const int i = i0 + g * RSTEP;
+              if (i < K) {
+                const double bi = rdlane(i < 64 ? bj0 : bj1, i & 63);
+                if (lane <= i) tri[i * (i + 1) / 2 + lane] = v[g] + bi * bj0;
+              }
+            }
+          }
+          // columns j = 64 + lane of the rows i >= 64
+#pragma unroll 1
+          for (int i0 = 64 + role; i0 < K; i0 += BBG * RSTEP) {
+            double v[BBG];
+#pragma unroll
+            for (int g = 0; g < BBG; ++g) {
+              const int i = i0 + g * RSTEP;
+              v[g] = (i < K && lane + 64 <= i) ? tri[i * (i + 1) / 2 + 64 + lane] : 0.0;
+            }
+#pragma unroll
+            for (int g = 0; g < BBG; ++g) {
+              const int i = i0 + g * RSTEP;
+              if (i < K) {
+                const double bi = rdlane(bj1, i & 63);
+                if (lane + 64 <= i) tri[i * (i + 1) / 2 + 64 + lane] = v[g] + bi * bj1;
+              }
+            }
+          }
+        }
       }
     }
 

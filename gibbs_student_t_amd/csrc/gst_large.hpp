@@ -309,6 +309,21 @@ __global__ void __launch_bounds__(LBLK) lg_accum(const DevModel* __restrict__ md
       if (A.resid_sq) A.resid_sq[rt + t] += y * y;
     }
   }
+  // gst_set_accum_block: the packed lower triangle of b b^T over the block's columns, one
+  // thread per packed element e = i (i + 1) / 2 + j (reference column order, as a.st.b holds it)
+  if (A.bb) {
+    const int K = A.bb_ncol, ne = K * (K + 1) / 2;
+    const double* bc = a.st.b + rb + A.bb_col0;
+    double* tri = A.bb + (size_t)c * ne;
+    for (int e = threadIdx.x; e < ne; e += LBLK) {
+      // row of e: the float root is within one of it for e < 2^15
+      int i = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+      if (i * (i + 1) / 2 > e) --i;
+      if ((i + 1) * (i + 2) / 2 <= e) ++i;
+      const int j = e - i * (i + 1) / 2;
+      tri[e] += bc[i] * bc[j];
+    }
+  }
   if (threadIdx.x == 0 && A.count) A.count[c] += 1;
 }
 

@@ -156,6 +156,11 @@ struct DevAccum {
   double thr[4];
   long long gt_plane;
   int nthr;
+  // gst_accum_block (gst_set_accum_block), null / 0 when unset: the packed lower triangle of
+  // b b^T over the columns [bb_col0, bb_col0 + bb_ncol) of b, bb_ncol (bb_ncol + 1) / 2 doubles
+  // per chain
+  int bb_col0, bb_ncol;
+  double* bb;
 };
 struct DevState {
   double *x, *b, *z, *alpha, *pout, *theta, *nu;

@@ -119,6 +119,9 @@ def fourier_basis(toas: np.ndarray, nmodes: int, Tspan: float | None = None):
 # ``<psr>_<keyword>_log10_A`` / ``<psr>_<keyword>_gamma``.
 CHROMATIC_GPS = (("dm_gp", 2), ("chrom_gp", 4))
 FREF_MHZ = 1400.0
+# enterprise.constants.DM_K: a delay of dt seconds at radio frequency nu (MHz) is a dispersion
+# measure of DM_K * nu^2 * dt pc cm^-3
+DM_K = 2.41e-4
 
 
 @dataclass(frozen=True)
@@ -216,6 +219,8 @@ class PTA:
         self._r = np.asarray(psr.residuals, dtype=np.float64)
         self._toaerrs = np.asarray(psr.toaerrs, dtype=np.float64)
         toas = np.asarray(psr.toas, dtype=np.float64)
+        # the ladder's span, remembered for process_basis at other epochs
+        self.Tspan = float(Tspan) if Tspan is not None else float(toas.max() - toas.min())
         self.F, self.Ffreqs = fourier_basis(toas, self.components, Tspan)
         # dispersion-measure / chromatic power laws: dict(components=, log10_A=(lo, hi),
         # gamma=(lo, hi)); their columns follow the red noise's, T = [red | dm | chrom | ...]
@@ -325,6 +330,7 @@ class PTA:
                              residuals=np.asarray(residuals), toaerrs=np.asarray(toaerrs),
                              Mmat=np.zeros((len(residuals), 0)))
         obj.components = int(components)
+        obj.Tspan = None                     # no epochs: process_basis raises
         obj._r = np.asarray(residuals, dtype=np.float64)
         obj._toaerrs = np.asarray(toaerrs, dtype=np.float64)
         # the Fourier block: [red | dm | chrom], Ffreqs each process's ladder in turn
@@ -447,6 +453,44 @@ class PTA:
                 return i
         return -1
 
+    def process_columns(self, name):
+        """``(lo, hi)``: the columns [lo, hi) of ``T`` (and of b) that the process ``name``
+        ("red", "dm_gp", "chrom_gp") owns."""
+        for pr in self.procs:
+            if pr.name == name:
+                return pr.col0, pr.col0 + pr.ncol
+        raise ValueError(f"unknown process {name!r}; this model has "
+                         f"{[pr.name for pr in self.procs]}")
+
+    def process_basis(self, name, toas=None, freqs=None, scaled=True):
+        """Fourier basis of the process ``name`` ("red", "dm_gp", "chrom_gp") at the epochs
+        ``toas`` (seconds) and radio frequencies ``freqs`` (MHz), on the model's own ladder
+        f_k = k / Tspan: [len(toas), 2 * components], the design matrix of the process's
+        waveform on any grid, between and beyond the TOAs.  Defaults: the model's TOAs and
+        their frequencies, where the result is bitwise the process's columns of ``T``.
+        ``scaled=False`` leaves out the ``(1400 MHz / nu)^chi`` weight of a chromatic process
+        (``freqs`` is then not needed): the delay at 1400 MHz, which times
+        ``DM_K * 1400^2`` (enterprise's ``DM_K = 2.41e-4``) is DM(t) in pc cm^-3 for
+        ``dm_gp``.  Like the rest of this module the formulas are restated from enterprise's
+        published form; parity against enterprise itself is **unpinned**.
+        A model rebuilt by ``from_arrays`` has neither epochs nor a span and raises."""
+        self.process_columns(name)           # an unknown process raises
+        pr = next(p_ for p_ in self.procs if p_.name == name)
+        if getattr(self, "Tspan", None) is None:
+            raise ValueError("process_basis: this model was rebuilt from arrays and has no "
+                             "epochs or span; build it from the pulsar (PTA(psr, ...))")
+        own = toas is None
+        toas = np.asarray(self.psr.toas if own else toas, dtype=np.float64)
+        F, _ = fourier_basis(toas, pr.components, self.Tspan)
+        if not scaled or pr.chi == 0:
+            return F
+        if freqs is None:
+            if not own:
+                raise ValueError(f"process_basis: {name} at other epochs needs freqs (MHz)")
+            freqs = self.psr.freqs
+        freqs = np.broadcast_to(np.asarray(freqs, dtype=np.float64), toas.shape)
+        return F * ((FREF_MHZ / freqs) ** pr.chi)[:, None]
+
     def sample_params(self):
         return np.array([p.sample() for p in self._params]).flatten()
 
@@ -479,6 +523,6 @@ def mh_constants():
 
 
 __all__ = ["Constant", "Uniform", "PulsarData", "PTA", "Process", "fourier_basis",
-           "chromatic_basis", "powerlaw", "CHROMATIC_GPS", "FREF_MHZ",
+           "chromatic_basis", "powerlaw", "CHROMATIC_GPS", "FREF_MHZ", "DM_K",
            "svd_tm_basis", "quantization_matrix", "df_tables", "hyper_white_indices", "mh_constants",
            "FYR", "YR_SEC", "DAY_SEC"]

@@ -20,6 +20,22 @@ STATE_KEYS = ("x", "b", "z", "alpha", "pout", "theta", "nu")
 ACCUM_KEYS = ("z_sum", "pout_sum", "alpha_sum", "b_sum", "b_sq", "count")
 # gst_accum_toa's buffers, in the struct's order (allocated on request)
 ACCUM_TOA_KEYS = ("pout_gt", "resid_sum", "resid_sq")
+# gst_accum_block's buffer (allocated on request, with b_block=(col0, ncol))
+ACCUM_BLOCK_KEY = "b_outer"
+
+
+def check_block(b_block, m):
+    """``(col0, ncol)`` as two ints: col0 >= 0, 1 <= ncol <= GST_BLOCK_MAX, col0 + ncol <= m."""
+    try:
+        col0, ncol = (int(v) for v in b_block)
+    except (TypeError, ValueError):
+        raise ValueError(f"b_block: need (col0, ncol), got {b_block!r}") from None
+    if col0 < 0 or ncol < 1 or col0 + ncol > m:
+        raise ValueError(f"b_block {(col0, ncol)}: columns must lie in [0, {m})")
+    if ncol > _abi.BLOCK_MAX:
+        raise ValueError(f"b_block {(col0, ncol)}: at most GST_BLOCK_MAX = {_abi.BLOCK_MAX} "
+                         "columns")
+    return col0, ncol
 
 
 def _check_thresholds(thr):
@@ -189,6 +205,7 @@ class NativeSampler:
         self.dataset = None
         self._accum = None
         self._accum_toa = None
+        self._accum_block = None
 
     def set_waves(self, waves="auto"):
         """Waves per chain of the persistent path's sampling launches (gst_set_waves):
@@ -269,37 +286,44 @@ class NativeSampler:
         return {k: torch.empty((self.C, nrec) + shapes[k], **f64) for k in keys}
 
     # ---- posterior sums (gst_set_accum, gst_set_accum_toa) ---------------------------
-    def _accum_shapes(self, nthr=None):
+    def _accum_shapes(self, nthr=None, b_block=None):
         sh = {"z_sum": (self.C, self.n), "pout_sum": (self.C, self.n),
               "alpha_sum": (self.C, self.n), "b_sum": (self.C, self.m),
               "b_sq": (self.C, self.m), "count": (self.C,),
               "resid_sum": (self.C, self.n), "resid_sq": (self.C, self.n)}
         if nthr:
             sh["pout_gt"] = (int(nthr), self.C, self.n)
+        if b_block is not None:
+            K = check_block(b_block, self.m)[1]
+            sh[ACCUM_BLOCK_KEY] = (self.C, K * (K + 1) // 2)
         return sh
 
-    def alloc_accum(self, keys=ACCUM_KEYS, pout_thresholds=None):
+    def alloc_accum(self, keys=ACCUM_KEYS, pout_thresholds=None, b_block=None):
         """Zeroed device tensors for the posterior sums: ``z_sum`` / ``pout_sum`` /
         ``alpha_sum`` [C, n], ``b_sum`` / ``b_sq`` [C, m] (float64) and ``count`` [C]
         (int64); on request ``pout_gt`` [K, C, n] (K = len(pout_thresholds)) and
-        ``resid_sum`` / ``resid_sq`` [C, n].  Pass the dict (or a subset of it) to
+        ``resid_sum`` / ``resid_sq`` [C, n], and with ``b_block=(col0, ncol)`` the key
+        ``b_outer`` [C, ncol (ncol + 1) / 2]: the packed lower triangle of sum b b^T over
+        the columns [col0, col0 + ncol) of b.  Pass the dict (or a subset of it) to
         ``set_accum``."""
         torch = _torch()
         thr = _check_thresholds(pout_thresholds)
-        shapes = self._accum_shapes(len(thr))
+        shapes = self._accum_shapes(len(thr), b_block)
         unknown = [k for k in keys if k not in shapes]
         if unknown:
             if unknown == ["pout_gt"]:
                 raise ValueError("pout_gt needs pout_thresholds")
+            if unknown == [ACCUM_BLOCK_KEY]:
+                raise ValueError("b_outer needs b_block=(col0, ncol)")
             raise ValueError(f"unknown accumulator(s) {unknown}; choose from "
-                             f"{ACCUM_KEYS + ACCUM_TOA_KEYS}")
+                             f"{ACCUM_KEYS + ACCUM_TOA_KEYS + (ACCUM_BLOCK_KEY,)}")
         return {k: torch.zeros(shapes[k], device=self.tdev,
                                dtype=torch.int64 if k == "count" else torch.float64)
                 for k in keys}
 
-    def _check_accum(self, acc, thr):
+    def _check_accum(self, acc, thr, b_block=None):
         torch = _torch()
-        shapes = self._accum_shapes(len(thr))
+        shapes = self._accum_shapes(len(thr), b_block)
         for k, t in acc.items():
             want = torch.int64 if k == "count" else torch.float64
             if k not in shapes or t.dtype != want or not t.is_contiguous() \
@@ -331,16 +355,43 @@ class NativeSampler:
                    "gst_set_accum_toa")
         self._accum_toa = toa
 
-    def set_accum(self, acc: dict, from_sweep: int = 0, pout_thresholds=None):
+    def set_accum_block(self, acc, b_block=None):
+        """gst_set_accum_block alone: the ``b_outer`` tensor of ``acc`` over the columns
+        ``b_block = (col0, ncol)`` (None or no such key: off).  It is added to only while
+        ``set_accum`` is set, from its ``from_sweep`` on."""
+        bo = acc.get(ACCUM_BLOCK_KEY) if acc else None
+        if not hasattr(self.lib, "gst_set_accum_block"):
+            if bo is not None:
+                raise _abi.GstNativeError("this libgst.so lacks gst_set_accum_block; rebuild")
+            return
+        if bo is None:
+            _abi.check(self.lib, self.lib.gst_set_accum_block(self.ctx, None),
+                       "gst_set_accum_block")
+            self._accum_block = None
+            return
+        if b_block is None:
+            raise ValueError("b_outer needs b_block=(col0, ncol)")
+        col0, ncol = check_block(b_block, self.m)
+        self._check_accum({ACCUM_BLOCK_KEY: bo}, (), (col0, ncol))
+        a = _abi.AccumBlock(col0, ncol, ct.c_void_p(bo.data_ptr()))
+        _abi.check(self.lib, self.lib.gst_set_accum_block(self.ctx, ct.byref(a)),
+                   "gst_set_accum_block")
+        self._accum_block = bo
+
+    def set_accum(self, acc: dict, from_sweep: int = 0, pout_thresholds=None, b_block=None):
         """Every later ``sweep`` adds the state at the start of each of its sweeps with global
         index ``sweep0 + i >= from_sweep`` into ``acc`` (tensors from ``alloc_accum``; missing
         keys are skipped), whatever ``record_every`` is, until ``clear_accum``.  With
         ``pout_gt`` in ``acc``, plane k counts the sweeps with ``pout > pout_thresholds[k]``
-        (up to 4 strictly increasing values in (0, 1)).  The sampler keeps ``acc`` referenced
+        (up to 4 strictly increasing values in (0, 1)); with ``b_outer`` in ``acc``,
+        ``b_block = (col0, ncol)`` names its columns.  The sampler keeps ``acc`` referenced
         while it is set."""
         thr = _check_thresholds(pout_thresholds)
-        self._check_accum(acc, thr)
+        if ACCUM_BLOCK_KEY in acc and b_block is None:
+            raise ValueError("b_outer needs b_block=(col0, ncol)")
+        self._check_accum(acc, thr, b_block if ACCUM_BLOCK_KEY in acc else None)
         self.set_accum_toa(acc, thr)
+        self.set_accum_block(acc, b_block)
         ptr = lambda k: ct.c_void_p(acc[k].data_ptr()) if k in acc else None  # noqa: E731
         a = _abi.Accum(*(ptr(k) for k in ACCUM_KEYS), int(from_sweep))
         _abi.check(self.lib, self.lib.gst_set_accum(self.ctx, ct.byref(a)), "gst_set_accum")
@@ -351,8 +402,12 @@ class NativeSampler:
         _abi.check(self.lib, self.lib.gst_set_accum(self.ctx, None), "gst_set_accum")
         if hasattr(self.lib, "gst_set_accum_toa"):
             _abi.check(self.lib, self.lib.gst_set_accum_toa(self.ctx, None), "gst_set_accum_toa")
+        if hasattr(self.lib, "gst_set_accum_block"):
+            _abi.check(self.lib, self.lib.gst_set_accum_block(self.ctx, None),
+                       "gst_set_accum_block")
         self._accum = None
         self._accum_toa = None
+        self._accum_block = None
 
     # ---- launches ------------------------------------------------------------------
     def stream_ptr(self):

@@ -16,6 +16,13 @@ All arrays are host numpy arrays with a leading chain axis: ``count`` [C] (int64
 ``z_sum`` / ``pout_sum`` / ``alpha_sum`` [C, n], ``b_sum`` / ``b_sq`` [C, m],
 ``resid_sum`` / ``resid_sq`` [C, n]; ``pout_gt`` is [K, C, n], one plane per threshold of
 ``pout_thr`` [K]; a sum that was not kept is ``None``.
+
+The spread of one process's waveform ``T_p b_p`` needs the covariance of b inside the process
+(include/gst.h gst_accum_block): ``b_outer`` [C, K (K + 1) / 2] is the packed lower triangle
+of the sum of ``b b^T`` over the columns ``b_block = (col0, K)`` of b, element (i, j), i >= j,
+at ``i (i + 1) / 2 + j``.  With ``b_sum`` and ``count`` it gives ``b_cov`` and, for any design
+matrix B over the block's columns, mean and standard deviation of ``B @ b`` (``waveform``,
+``process_waveform``).
 """
 from __future__ import annotations
 
@@ -25,15 +32,19 @@ SUM_KEYS = ("z_sum", "pout_sum", "alpha_sum", "b_sum", "b_sq")
 # the sums of gst_accum_toa: after SUM_KEYS wherever the sums are listed in order, so that
 # a PosteriorSums without them looks (pooled vector, files) as it always did
 TOA_KEYS = ("pout_gt", "resid_sum", "resid_sq")
+# the sum of gst_accum_block: after every other key, for the same reason
+BLOCK_KEYS = ("b_outer",)
+ALL_KEYS = SUM_KEYS + TOA_KEYS + BLOCK_KEYS
 
 
 class PosteriorSums:
     def __init__(self, count, z_sum=None, pout_sum=None, alpha_sum=None, b_sum=None, b_sq=None,
-                 pout_thr=None, pout_gt=None, resid_sum=None, resid_sq=None):
+                 pout_thr=None, pout_gt=None, resid_sum=None, resid_sq=None, b_outer=None,
+                 b_block=None):
         self.count = np.atleast_1d(np.asarray(count, dtype=np.int64))
         C = self.count.shape[0]
-        for key, v in zip(SUM_KEYS + TOA_KEYS[1:],
-                          (z_sum, pout_sum, alpha_sum, b_sum, b_sq, resid_sum, resid_sq)):
+        for key, v in zip(SUM_KEYS + TOA_KEYS[1:] + BLOCK_KEYS,
+                          (z_sum, pout_sum, alpha_sum, b_sum, b_sq, resid_sum, resid_sq, b_outer)):
             if v is not None:
                 v = np.asarray(v, dtype=np.float64)
                 if v.ndim != 2 or v.shape[0] != C:
@@ -48,16 +59,30 @@ class PosteriorSums:
                 raise ValueError(f"pout_gt: need [K = {pout_thr.shape[0]}, C = {C}, n], "
                                  f"got {pout_gt.shape}")
         self.pout_thr, self.pout_gt = pout_thr, pout_gt
+        if (b_outer is None) != (b_block is None):
+            raise ValueError("b_outer and b_block go together")
+        if b_block is not None:
+            b_block = tuple(int(v) for v in np.asarray(b_block).reshape(-1))
+            if len(b_block) != 2 or b_block[0] < 0 or b_block[1] < 1:
+                raise ValueError(f"b_block: need (col0, ncol), got {b_block}")
+            K = b_block[1]
+            if self.b_outer.shape[1] != K * (K + 1) // 2:
+                raise ValueError(f"b_outer: need [C = {C}, {K * (K + 1) // 2}] for a block of "
+                                 f"{K} columns, got {self.b_outer.shape}")
+        self.b_block = b_block
 
     @classmethod
-    def from_device(cls, acc: dict, pout_thresholds=None):
+    def from_device(cls, acc: dict, pout_thresholds=None, b_block=None):
         """From ``NativeSampler.alloc_accum`` tensors (synchronises the device);
-        ``pout_thresholds``: the thresholds of ``acc["pout_gt"]``'s planes."""
+        ``pout_thresholds``: the thresholds of ``acc["pout_gt"]``'s planes; ``b_block``: the
+        ``(col0, ncol)`` of ``acc["b_outer"]``."""
         host = {k: v.detach().cpu().numpy() for k, v in acc.items()}
         if "count" not in host:
             raise ValueError("the accumulators need 'count'")
         if "pout_gt" in host:
             host["pout_thr"] = pout_thresholds
+        if "b_outer" in host:
+            host["b_block"] = b_block
         return cls(**host)
 
     @property
@@ -163,9 +188,74 @@ class PosteriorSums:
         m = self._mean("resid_sum", pool)
         return np.sqrt(np.maximum(self._mean("resid_sq", pool) - m * m, 0.0))
 
+    # ---- block second moment: covariance of b, waveforms with bands -------------------
+    def _block_moments(self, pool):
+        """(mu [.., K], M [.., K, K]) of the block: mean of b and of b b^T over the counted
+        sweeps, pooled over all chains' sweeps or per chain (leading axis C)."""
+        bo = self._get("b_outer")
+        col0, K = self.b_block
+        bs = self._get("b_sum")[:, col0:col0 + K]
+        if pool:
+            N = self.count.sum()
+            tri, mu = bo.sum(axis=0) / N, bs.sum(axis=0) / N
+        else:
+            tri, mu = bo / self.count[:, None], bs / self.count[:, None]
+        i, j = np.tril_indices(K)      # row-major lower triangle: e = i (i + 1) / 2 + j
+        M = np.zeros(tri.shape[:-1] + (K, K))
+        M[..., i, j] = tri
+        M[..., j, i] = tri
+        return mu, M
+
+    def b_cov(self, pool=True):
+        """Covariance of the block's coefficients over the counted sweeps (population form,
+        E b b^T - E b E b^T): [K, K] pooled over all chains' sweeps, or [C, K, K] per chain."""
+        mu, M = self._block_moments(pool)
+        return M - mu[..., :, None] * mu[..., None, :]
+
+    def waveform(self, B, cols=None, pool=True):
+        """``(mean, sd)`` of ``B @ b[cols]`` over the counted sweeps: ``B`` [T, k] is a design
+        matrix over the block's columns ``cols`` (a slice relative to the block's first
+        column; default: the whole block); sd = sqrt(max(diag(B Cov B^T), 0)), population
+        form.  [T] each, or [C, T] per chain."""
+        B = np.asarray(B, dtype=np.float64)
+        mu, M = self._block_moments(pool)
+        cov = M - mu[..., :, None] * mu[..., None, :]
+        if cols is not None:
+            if not isinstance(cols, slice) or cols.step not in (None, 1):
+                raise ValueError("cols: a contiguous slice inside the block")
+            mu, cov = mu[..., cols], cov[..., cols, cols]
+        if B.ndim != 2 or B.shape[1] != mu.shape[-1]:
+            raise ValueError(f"B: need [T, {mu.shape[-1]}], got {B.shape}")
+        mean = mu @ B.T
+        var = np.einsum("ti,...ij,tj->...t", B, cov, B)
+        return mean, np.sqrt(np.maximum(var, 0.0))
+
+    def process_waveform(self, pta, name, toas=None, freqs=None, units="s", pool=True):
+        """``(mean, sd)`` of the waveform of the process ``name`` ("red", "dm_gp", "chrom_gp")
+        of ``pta`` (model.PTA) at the epochs ``toas`` and radio frequencies ``freqs`` (default:
+        the model's own), from ``PTA.process_basis``; the block must cover the process.
+        ``units="s"``: the delay in seconds as it enters the residuals; ``units="dm"``: the
+        process without its (1400 / nu)^chi weight times 2.41e-4 * 1400^2, i.e. DM in
+        pc cm^-3 for ``dm_gp`` (see ``PTA.process_basis`` on parity)."""
+        if units not in ("s", "dm"):
+            raise ValueError('units must be "s" or "dm"')
+        self._get("b_outer")
+        lo, hi = pta.process_columns(name)
+        col0, K = self.b_block
+        if lo < col0 or hi > col0 + K:
+            raise ValueError(f"process {name!r} owns columns [{lo}, {hi}), the block kept "
+                             f"[{col0}, {col0 + K})")
+        B = pta.process_basis(name, toas=toas, freqs=freqs, scaled=units == "s")
+        if units == "dm":
+            from .model import DM_K
+            B = B * (DM_K * 1400.0 ** 2)
+        return self.waveform(B, cols=slice(lo - col0, hi - col0), pool=pool)
+
     # ---- merging -------------------------------------------------------------------
     def _same_kept(self, other):
-        for key in SUM_KEYS + TOA_KEYS:
+        if self.b_block != other.b_block:
+            raise ValueError(f"b blocks differ: {self.b_block} and {other.b_block}")
+        for key in ALL_KEYS:
             if (getattr(self, key) is None) != (getattr(other, key) is None):
                 raise ValueError(f"{key} is kept by one operand only")
         if self.pout_gt is not None and not np.array_equal(self.pout_thr, other.pout_thr):
@@ -181,60 +271,64 @@ class PosteriorSums:
                              "use concat() for other chains")
         self._same_kept(other)
         kw = {key: None if getattr(self, key) is None else getattr(self, key) + getattr(other, key)
-              for key in SUM_KEYS + TOA_KEYS}
-        return PosteriorSums(self.count + other.count, pout_thr=self.pout_thr, **kw)
+              for key in ALL_KEYS}
+        return PosteriorSums(self.count + other.count, pout_thr=self.pout_thr,
+                             b_block=self.b_block, **kw)
 
     def concat(self, other):
         """Sums of other chains of the same model (another rank's shard) appended."""
         self._same_kept(other)
         kw = {}
-        for key in SUM_KEYS + TOA_KEYS:
+        for key in ALL_KEYS:
             a, b = getattr(self, key), getattr(other, key)
             kw[key] = None if a is None else np.concatenate([a, b], axis=a.ndim - 2)
         return PosteriorSums(np.concatenate([self.count, other.count]), pout_thr=self.pout_thr,
-                             **kw)
+                             b_block=self.b_block, **kw)
 
     def select(self, chains, n=None):
         """The sums of the chains ``chains`` (indices or a slice), per-TOA arrays cut to their
         first ``n`` entries (a batch's dataset with fewer TOAs than the batch's stride)."""
         kw = {}
-        for key in SUM_KEYS + TOA_KEYS:
+        for key in ALL_KEYS:
             v = getattr(self, key)
             if v is not None:
                 v = v[..., chains, :]
-                if n is not None and key not in ("b_sum", "b_sq"):
+                if n is not None and key not in ("b_sum", "b_sq", "b_outer"):
                     v = v[..., :n]
             kw[key] = v
-        return PosteriorSums(self.count[chains], pout_thr=self.pout_thr, **kw)
+        return PosteriorSums(self.count[chains], pout_thr=self.pout_thr, b_block=self.b_block,
+                             **kw)
 
     # ---- pooled form (what ranks exchange) -------------------------------------------
     def pooled(self):
         """The sums over this object's chains as one pseudo-chain ``PosteriorSums`` (C = 1):
         every pooled mean is unchanged, and pooled sums of several ranks merge with ``+``."""
         kw = {}
-        for k in SUM_KEYS + TOA_KEYS:
+        for k in ALL_KEYS:
             v = getattr(self, k)
             kw[k] = None if v is None else v.sum(axis=v.ndim - 2, keepdims=True)
-        return PosteriorSums([self.count.sum()], pout_thr=self.pout_thr, **kw)
+        return PosteriorSums([self.count.sum()], pout_thr=self.pout_thr, b_block=self.b_block,
+                             **kw)
 
     def pooled_vector(self):
         """``pooled()`` as one flat float64 vector [total count | the kept sums in SUM_KEYS
-        order | pout_gt plane by plane, resid_sum, resid_sq where kept]: what
+        order | pout_gt plane by plane, resid_sum, resid_sq, b_outer where kept]: what
         ``dist.reduce_summary`` adds over the ranks (counts stay exact below 2^53)."""
         p = self.pooled()
         parts = [p.count.astype(np.float64)]
         parts += [getattr(p, k)[0] for k in SUM_KEYS if getattr(p, k) is not None]
         if p.pout_gt is not None:
             parts.append(p.pout_gt.reshape(-1))
-        parts += [getattr(p, k)[0] for k in TOA_KEYS[1:] if getattr(p, k) is not None]
+        parts += [getattr(p, k)[0] for k in TOA_KEYS[1:] + BLOCK_KEYS
+                  if getattr(p, k) is not None]
         return np.concatenate(parts)
 
     def from_pooled_vector(self, vec):
         """A reduced ``pooled_vector()`` back as a C = 1 ``PosteriorSums`` with this object's
-        kept sums, thresholds and sizes."""
+        kept sums, thresholds, block and sizes."""
         vec = np.asarray(vec, dtype=np.float64)
         kw, o = {}, 1
-        for k in SUM_KEYS + TOA_KEYS:
+        for k in ALL_KEYS:
             v = getattr(self, k)
             if v is None:
                 continue
@@ -248,7 +342,8 @@ class PosteriorSums:
                 o += w
         if o != vec.shape[0]:
             raise ValueError(f"vector of {vec.shape[0]} entries, expected {o}")
-        return PosteriorSums([int(round(vec[0]))], pout_thr=self.pout_thr, **kw)
+        return PosteriorSums([int(round(vec[0]))], pout_thr=self.pout_thr,
+                             b_block=self.b_block, **kw)
 
     # ---- files ---------------------------------------------------------------------
     def save(self, path):
@@ -257,6 +352,9 @@ class PosteriorSums:
                   if getattr(self, k) is not None}
         if self.pout_gt is not None:
             arrays["pout_thr"] = self.pout_thr
+        if self.b_outer is not None:
+            arrays["b_outer"] = self.b_outer
+            arrays["b_block"] = np.asarray(self.b_block, dtype=np.int64)
         np.savez(path, count=self.count, **arrays)
 
     @classmethod

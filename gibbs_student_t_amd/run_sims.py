@@ -192,7 +192,8 @@ class Study:
         return self.entry0 * self.chains
 
     def run(self, niter, burn=100, outdir=None, chunk=500, record_every=1, keys=None,
-            progress=None, accumulate=False, pout_thresholds=None, signal_band=False):
+            progress=None, accumulate=False, pout_thresholds=None, signal_band=False,
+            b_cov=None):
         """Sample ``niter`` sweeps; write [burn:] records per entry under ``outdir``.
 
         Returns ``(records or None, seconds)``: without ``outdir`` the post-burn records
@@ -201,22 +202,31 @@ class Study:
         ``keys`` restricts the recorded arrays (default: all of CHAIN_FILES; may be empty).
         ``accumulate``: keep the posterior sums (post.PosteriorSums) of every sweep from
         ``burn`` on, whatever ``record_every`` is -- with ``pout_thresholds`` the per-TOA
-        exceedance counts of pout, with ``signal_band`` the sums of y = r - T b and y^2 --
+        exceedance counts of pout, with ``signal_band`` the sums of y = r - T b and y^2, with
+        ``b_cov`` (as ``Gibbs.sample``'s: a process name, a tuple of names, "fourier", "all"
+        or ``(col0, ncol)``; the batch's models share one column layout) the second moment of
+        b inside that block of columns --
         leave them in ``self.post`` (all chains, row stride ``ns.n``) and, with ``outdir``,
         save each entry's as ``post.npz`` beside its chain files (its chains, per-TOA arrays
         cut to its n)."""
         ns, C = self.ns, self.chains
-        if (pout_thresholds is not None or signal_band) and not accumulate:
-            raise ValueError("pout_thresholds and signal_band need accumulate=True")
+        if (pout_thresholds is not None or signal_band or b_cov is not None) and not accumulate:
+            raise ValueError("pout_thresholds, signal_band and b_cov need accumulate=True")
+        block = None
+        if b_cov is not None:
+            from .sampler import b_cov_block
+            block = b_cov_block(self.entries[0].pta, b_cov)
         keys = [k for k, _ in CHAIN_FILES] if keys is None else list(keys)
         acc = None
         if accumulate:
             from .native import ACCUM_KEYS
             extra = (("pout_gt",) if pout_thresholds is not None else ()) + \
-                (("resid_sum", "resid_sq") if signal_band else ())
-            acc = ns.alloc_accum(ACCUM_KEYS + extra, pout_thresholds=pout_thresholds)
+                (("resid_sum", "resid_sq") if signal_band else ()) + \
+                (("b_outer",) if block is not None else ())
+            acc = ns.alloc_accum(ACCUM_KEYS + extra, pout_thresholds=pout_thresholds,
+                                 b_block=block)
             ns.set_accum(acc, from_sweep=self.sweeps_done + int(burn),
-                         pout_thresholds=pout_thresholds)
+                         pout_thresholds=pout_thresholds, b_block=block)
         try:
             out = self._run(niter, burn, outdir, chunk, record_every, keys, progress)
         finally:
@@ -224,7 +234,7 @@ class Study:
                 ns.clear_accum()
         if accumulate:
             from .post import PosteriorSums
-            self.post = PosteriorSums.from_device(acc, pout_thresholds)
+            self.post = PosteriorSums.from_device(acc, pout_thresholds, block)
             if outdir is not None:
                 for i, e in enumerate(self.entries):
                     d = e.outdir(outdir)
@@ -421,9 +431,16 @@ def main(argv=None):
     ap.add_argument("--signal-band", action="store_true",
                     help="with --post: sums of y = r - T b and y^2 (mean and spread of the "
                          "signal at every TOA)")
+    ap.add_argument("--b-cov", nargs="+", default=None, metavar="NAME",
+                    help="with --post: the second moment of b inside the columns of the named "
+                         "process(es) (red, dm_gp, chrom_gp: the smallest range covering them), "
+                         "or fourier / all -- a process's waveform with its band "
+                         "(post.process_waveform)")
     args = ap.parse_args(argv)
-    if (args.pout_thresholds is not None or args.signal_band) and not args.post:
-        ap.error("--pout-thresholds and --signal-band need --post")
+    if (args.pout_thresholds is not None or args.signal_band or args.b_cov) and not args.post:
+        ap.error("--pout-thresholds, --signal-band and --b-cov need --post")
+    b_cov = None if not args.b_cov else \
+        (args.b_cov[0] if len(args.b_cov) == 1 else tuple(args.b_cov))
     from . import dist
     rank, local, world = dist.init()
     dofs = tuple([None] + list(args.dofs)) if args.dofs else (None,)
@@ -439,7 +456,8 @@ def main(argv=None):
                vvh17_start=args.vvh17_start)
     recs, secs = st.run(args.niter, burn=args.burn, outdir=args.outdir, chunk=args.chunk,
                         record_every=args.record_every, keys=args.keys, accumulate=args.post,
-                        pout_thresholds=args.pout_thresholds, signal_band=args.signal_band)
+                        pout_thresholds=args.pout_thresholds, signal_band=args.signal_band,
+                        b_cov=b_cov)
     total = len(mine) * args.chains * args.niter
     print(json.dumps({"rank": rank, "entries": len(mine), "chains": args.chains,
                       "sweeps": args.niter, "vvh17_start": args.vvh17_start, "seconds": secs,

@@ -7,7 +7,9 @@ chain arrays gain a leading chain axis when > 1), ``seed`` (Philox key), ``devic
 ``sample`` takes ``record`` (which chain arrays to keep), ``accumulate`` and ``burn`` (posterior
 sums kept on the device, left in ``self.post``: post.PosteriorSums), and with them
 ``pout_thresholds`` (per-TOA counts of pout above each threshold: the notebook's median rule)
-and ``signal_band`` (sums of y = r - T b and y^2: the signal's spread at every TOA).
+and ``signal_band`` (sums of y = r - T b and y^2: the signal's spread at every TOA) and
+``b_cov`` (the second moment of b inside a block of columns: one process's waveform with its
+band, on any grid).
 
 Differences from the reference, all documented in DESIGN.md:
 * ``update_b`` recomputes T^T N^-1 T from the current state; the reference reuses whatever
@@ -31,7 +33,39 @@ import numpy as np
 import scipy.special
 
 from . import _abi
-from .native import STATE_KEYS, NativeSampler
+from .native import STATE_KEYS, NativeSampler, check_block
+
+
+def b_cov_block(pta, spec):
+    """The columns ``(col0, ncol)`` of b that ``Gibbs.sample(b_cov=spec)`` keeps the second
+    moment of: a process name ("red", "dm_gp", "chrom_gp"), a tuple of names (the smallest
+    contiguous range covering them: the processes are contiguous in [red | dm | chrom]),
+    "fourier" (the whole Fourier block), "all" (every column of b) or an explicit
+    ``(col0, ncol)``.  Raises ValueError for a process the model lacks, a range outside b or
+    more than GST_BLOCK_MAX columns."""
+    m = int(pta.get_basis()[0].shape[1])
+    procs = {pr.name: pr for pr in getattr(pta, "procs", ())}
+
+    def cols(name):
+        if name not in procs:
+            raise ValueError(f"b_cov: unknown process {name!r}; this model has {list(procs)}")
+        return procs[name].col0, procs[name].col0 + procs[name].ncol
+
+    if isinstance(spec, str):
+        if spec == "all":
+            block = (0, m)
+        elif spec == "fourier":
+            block = (0, int(pta.nfourier))
+        else:
+            lo, hi = cols(spec)
+            block = (lo, hi - lo)
+    elif isinstance(spec, (tuple, list)) and spec and all(isinstance(v, str) for v in spec):
+        rng = [cols(v) for v in spec]
+        lo, hi = min(r[0] for r in rng), max(r[1] for r in rng)
+        block = (lo, hi - lo)
+    else:
+        block = spec
+    return check_block(block, m)
 
 
 class Gibbs:
@@ -205,7 +239,7 @@ class Gibbs:
 
     # ---- the sampler (gibbs.py:342-385) ----------------------------------------------------
     def sample(self, xs, niter=10000, *, record=None, accumulate=False, burn=0,
-               pout_thresholds=None, signal_band=False):
+               pout_thresholds=None, signal_band=False, b_cov=None):
         """gibbs.py:342-385.  ``record``: the chain arrays to keep, a subset of ("x", "b",
         "z", "alpha", "pout", "theta", "nu") (default: all, as the reference); an omitted array
         is allocated neither on the host nor on the device, is not copied, and its attribute
@@ -218,9 +252,14 @@ class Gibbs:
         the number of sweeps with ``pout > threshold`` -- what the notebook's median rule
         ``np.median(poutchain, axis=0) > tau`` needs (``post.outliers(tau, rule="median")``)
         -- and ``signal_band`` the sums of y = r - T b and y^2, the mean and spread of the
-        signal at every TOA (``post.signal_mean_toa``, ``post.signal_sd``)."""
-        if (pout_thresholds is not None or signal_band) and not accumulate:
-            raise ValueError("pout_thresholds and signal_band need accumulate=True")
+        signal at every TOA (``post.signal_mean_toa``, ``post.signal_sd``); ``b_cov`` (a process
+        name, a tuple of names, "fourier", "all" or ``(col0, ncol)``: ``b_cov_block``) the
+        second moment of b inside that block of columns, from which ``post.b_cov``,
+        ``post.waveform`` and ``post.process_waveform`` give one process's waveform with its
+        band at the TOAs or on any grid."""
+        if (pout_thresholds is not None or signal_band or b_cov is not None) and not accumulate:
+            raise ValueError("pout_thresholds, signal_band and b_cov need accumulate=True")
+        block = None if b_cov is None else b_cov_block(self.pta, b_cov)
         C, P = self.nchains, len(self.params)
         n, mcols = len(self._residuals), self._b_all.shape[1]
         every = max(1, self.record_every)
@@ -241,10 +280,12 @@ class Gibbs:
         if accumulate:
             from .native import ACCUM_KEYS
             extra = (("pout_gt",) if pout_thresholds is not None else ()) + \
-                (("resid_sum", "resid_sq") if signal_band else ())
-            acc = self._native.alloc_accum(ACCUM_KEYS + extra, pout_thresholds=pout_thresholds)
+                (("resid_sum", "resid_sq") if signal_band else ()) + \
+                (("b_outer",) if block is not None else ())
+            acc = self._native.alloc_accum(ACCUM_KEYS + extra, pout_thresholds=pout_thresholds,
+                                           b_block=block)
             self._native.set_accum(acc, from_sweep=self._sweep_counter + int(burn),
-                                   pout_thresholds=pout_thresholds)
+                                   pout_thresholds=pout_thresholds, b_block=block)
         try:
             chunk = max(every, (self.chunk // every) * every)
             tstart = time.time()
@@ -275,7 +316,7 @@ class Gibbs:
         x = self._pull()
         if accumulate:
             from .post import PosteriorSums
-            self.post = PosteriorSums.from_device(acc, pout_thresholds)
+            self.post = PosteriorSums.from_device(acc, pout_thresholds, block)
         self._counter_at_sample = self._sweep_counter
         return x[0] if C == 1 else x
 

@@ -242,6 +242,30 @@ typedef struct gst_accum_toa {
   double* resid_sq;   /* [C][nmax]  sum of y_t^2 */
 } gst_accum_toa;
 
+/* Block second moment of b (additive to ABI 7: callers find gst_set_accum_block by symbol
+ * lookup).  b_sq is only the diagonal of sum_i b b^T; the spread of a process's waveform
+ * T_p b_p needs the covariance of b inside the process, whose columns are strongly correlated
+ * (sin / cos pairs, steep spectra).  bb keeps the lower triangle of sum_i b b^T over the
+ * columns [col0, col0 + ncol) of b (reference column order, as gst_state.b and b_sum hold it):
+ * element (i, j), i >= j both relative to col0, of launch-local chain c lies at
+ * bb[c * ncol (ncol + 1) / 2 + i (i + 1) / 2 + j].  With b_sum and count it gives the
+ * posterior covariance of the block's coefficients, hence mean and variance of B b for any
+ * design matrix B (the process basis at the TOAs or on a dense grid).  A DEVICE pointer,
+ * caller-owned and caller-zeroed; bb NULL switches the block off.  col0 >= 0,
+ * 1 <= ncol <= GST_BLOCK_MAX and col0 + ncol <= m of the model set (setting a block before
+ * gst_model_set* is an error; a later gst_model_set* switches it off).
+ * The semantics are gst_accum's and there is no second from_sweep or count: the sums are kept
+ * only while gst_set_accum is set, from its from_sweep on, on every counted sweep whatever
+ * record_every is, one owner per element as a plain sum = sum + b_i * b_j (which may be
+ * fused) of the start-of-sweep b in sweep order; gst_eval_lnlike and GST_STAGE_GRAM launches
+ * never add; a chain the persistent path does not run (status bit 2) is left untouched.  With
+ * gst_set_accum unset nothing is written. */
+#define GST_BLOCK_MAX 256
+typedef struct gst_accum_block {
+  int col0, ncol;     /* columns [col0, col0 + ncol) of b, reference column order */
+  double* bb;         /* [C][ncol (ncol + 1) / 2] packed lower triangle, or NULL */
+} gst_accum_block;
+
 int gst_version(void);
 int gst_tape_stride(int n, int m);
 int gst_last_error(char* buf, size_t len);
@@ -301,6 +325,11 @@ int gst_set_accum(void* ctx, const gst_accum* acc);
 /* Exceedance counts and residual sums (gst_accum_toa above): *a is copied; NULL switches them
  * off.  Kept only while gst_set_accum is set; takes effect from the next gst_sweep call. */
 int gst_set_accum_toa(void* ctx, const gst_accum_toa* a);
+
+/* Block second moment of b (gst_accum_block above): *blk is copied; NULL switches it off.
+ * Kept only while gst_set_accum is set; takes effect from the next gst_sweep call, in stream
+ * order with it.  Errors (< 0, gst_last_error) leave the block as it was. */
+int gst_set_accum_block(void* ctx, const gst_accum_block* blk);
 
 int gst_sync(void* ctx, void* stream);
 

@@ -10,11 +10,17 @@ timed with device events after a warm-up launch:
     accum       all six accumulators set, no records
     accum_toa   sums + thresholds (K = 2) + band: the six, pout_gt at two thresholds and
                 resid_sum / resid_sq (gst_set_accum_toa; skipped on a library without it)
+    accum_block20 / accum_block60
+                the six plus the block second moment of b (gst_set_accum_block) over the
+                columns [0, 20) (a dm_gp-sized block) and [0, 60) (the whole Fourier block):
+                2 * 8 * K (K + 1) / 2 more bytes per chain-sweep; skipped on a library
+                without the entry point
     rec_every10 z / alpha / pout / b recorded every 10th sweep on the device
     rec_full    ... every sweep (the large-path run cut to the sweeps whose records fit)
 
 GST_LIB=<another build's libgst.so> times that build with the same driver (a parent build for
-comparison; --large-repeats 3 gives the large-path rows a spread to compare against).
+comparison; --large-repeats 3 gives the large-path rows a spread to compare against;
+--rows off accum ... times only those rows).
 
 Records are timed on the device only: the copy to the host that Gibbs.sample adds is not in
 these numbers.
@@ -41,7 +47,15 @@ def has_toa(ns):
     return hasattr(ns.lib, "gst_set_accum_toa")
 
 
-def timed(ns, S, *, accum=False, toa=False, record_every=0, seed=1, warm=8):
+BLOCKS = {"accum_block20": (0, 20), "accum_block60": (0, 60)}
+ROWS = ("off", "accum", "accum_toa") + tuple(BLOCKS) + ("rec_every10", "rec_full")
+
+
+def has_block(ns):
+    return hasattr(ns.lib, "gst_set_accum_block")
+
+
+def timed(ns, S, *, accum=False, toa=False, block=None, record_every=0, seed=1, warm=8):
     """ms per sweep of one S-sweep launch (device events), after a warm-up launch."""
     import torch
     ns.sweep(warm, seed=seed)
@@ -50,6 +64,10 @@ def timed(ns, S, *, accum=False, toa=False, record_every=0, seed=1, warm=8):
         from gibbs_student_t_amd.native import ACCUM_KEYS, ACCUM_TOA_KEYS
         acc = ns.alloc_accum(ACCUM_KEYS + ACCUM_TOA_KEYS, pout_thresholds=TOA_THR)
         ns.set_accum(acc, from_sweep=warm, pout_thresholds=TOA_THR)
+    elif accum and block:
+        from gibbs_student_t_amd.native import ACCUM_KEYS
+        acc = ns.alloc_accum(ACCUM_KEYS + ("b_outer",), b_block=block)
+        ns.set_accum(acc, from_sweep=warm, b_block=block)
     elif accum:
         acc = ns.alloc_accum()
         ns.set_accum(acc, from_sweep=warm)
@@ -66,16 +84,19 @@ def timed(ns, S, *, accum=False, toa=False, record_every=0, seed=1, warm=8):
     return e0.elapsed_time(e1) / S
 
 
-def measure(make, S, S_full, repeats=3):
+def measure(make, S, S_full, repeats=3, rows=ROWS):
     out = {}
     for label, kw, sweeps in (("off", {}, S), ("accum", dict(accum=True), S),
                               ("accum_toa", dict(accum=True, toa=True), S),
+                              *((k, dict(accum=True, block=v), S) for k, v in BLOCKS.items()),
                               ("rec_every10", dict(record_every=10), S),
                               ("rec_full", dict(record_every=1), S_full)):
+        if label not in rows:
+            continue
         ms = []
         for _ in range(repeats):
             ns = make()
-            if kw.get("toa") and not has_toa(ns):
+            if (kw.get("toa") and not has_toa(ns)) or (kw.get("block") and not has_block(ns)):
                 ns.close()
                 break
             ms.append(timed(ns, sweeps, **kw))
@@ -83,8 +104,8 @@ def measure(make, S, S_full, repeats=3):
         if ms:
             out[label] = {"sweeps": sweeps, "ms_per_sweep": sorted(ms),
                           "median_ms_per_sweep": float(np.median(ms))}
-    for label in ("accum", "accum_toa", "rec_every10", "rec_full"):
-        if label in out:
+    for label in ROWS[1:]:
+        if label in out and "off" in out:
             out[label]["over_off"] = \
                 out[label]["median_ms_per_sweep"] / out["off"]["median_ms_per_sweep"]
     return out
@@ -98,6 +119,8 @@ def main():
                     help="sweeps of the large path's full-record run (316 KB per chain-sweep)")
     ap.add_argument("--large-repeats", type=int, default=1,
                     help="repeats of each large-path row (3: a spread to compare builds against)")
+    ap.add_argument("--rows", nargs="+", default=list(ROWS), choices=ROWS,
+                    help="the rows to time (default: all)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "accum_cost.json"))
     a = ap.parse_args()
     import bench
@@ -128,10 +151,10 @@ def main():
 
     res = {"sweeps": a.sweeps,
            "config2": dict(chains=wl["C"], n=int(wl["ptas"][0].n), path="persistent",
-                           **measure(config2, a.sweeps, a.sweeps)),
+                           **measure(config2, a.sweeps, a.sweeps, rows=a.rows)),
            "j1643_like": dict(chains=C, n=int(pta.n), path="large",
                               **measure(j1643, a.sweeps, a.large_full_sweeps,
-                                        repeats=a.large_repeats))}
+                                        repeats=a.large_repeats, rows=a.rows))}
     print(json.dumps(res))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
